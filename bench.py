@@ -17,18 +17,17 @@ Prints ONE JSON line (rank 0).  Extra objects:
   roofline      dominant kernel, algorithmic FLOPs / HIP-event time vs the f32 MFMA peak
   cpu_baseline  oracle/fine_path.py (the CPU port of the reference path) timed on
                 the host cores on a bounded ray sample of the same scene (N=1 only)
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned
+(loss, every parameter gradient, and the LTS steps' forward outputs) as DIR/<name>.npy, float32
+or float64, at most 64 MB in all: arrays too large for that are cut to a seeded sample of their
+elements that depends only on the array's name and size, so two builds can be compared file by file.
 """
 import argparse
 import json
 import os
 import sys
 import time
-
-# HIP multiplexes its streams onto GPU_MAX_HW_QUEUES hardware queues (default 4).  With an RCCL communicator alive its
-# streams take queues too, and the engine's side stream (weight gradients beside the grid scatters, packing beside the
-# march) landed on the SAME in-order hardware queue as the main stream: everything serialised, +0.12 ms per step
-# (tools/trace_step.py on `bench.py --force-dist`: one queue id for all kernels).  Must be set before HIP initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import torch
 
@@ -72,7 +71,7 @@ RAD_MAC, TONE_MAC = net_macs("off", "fwd"), net_macs("tone", "fwd")
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="C2", choices=["C2", "C3", "C4", "C5", "small", "tiny"],
                     help="BASELINE.json configs: C2 fine fp32 (headline), C3 fine 192 samples, C4 lts, C5 = C4 scene, pdra stage, "
@@ -121,7 +120,54 @@ def parse():
     ap.add_argument("--no-other", action="store_true",
                     help="headline run only: skip the `other_workloads` key (C3 bf16, C4 lts f32, C5 pdra bf16; 30 steps each, "
                          "one child process per workload after the headline has been measured)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
+    return a
+
+
+DUMP_BYTES = 60_000_000           # data of all .npy files of --dump-outputs (their headers come on top: < 64 MB)
+DUMP_SEED = 20240917
+
+
+def dump_arrays(res):
+    """The step's result (loss, {parameter: gradient}[, {output: tensor}]) as {file name: tensor}."""
+    arrays = {"loss": res[0]}
+    for prefix, d in zip(("grad", "out"), res[1:3]):
+        for k, v in d.items():
+            if torch.is_tensor(v):
+                arrays[f"{prefix}.{k.replace('/', '.')}"] = v
+    return arrays
+
+
+def dump_index(name, n, k):
+    """Sorted distinct flat indices from a seeded draw of ``k`` of ``n``: the same for the same name, n and k in every run."""
+    import zlib
+    import numpy as np
+    rng = np.random.default_rng([DUMP_SEED, zlib.crc32(name.encode())])
+    return np.unique(rng.integers(0, n, size=k))
+
+
+def dump_sample(arrays, budget=DUMP_BYTES):
+    """Copy the arrays to the host as float32 (float64 / integer arrays: float64, exact), within ``budget`` bytes: the
+    smallest arrays whole, the budget left shared equally by the rest, each of those cut to its elements at
+    ``dump_index`` (flat, row-major positions)."""
+    out, names = {}, sorted(arrays, key=lambda k: (arrays[k].numel(), k))
+    for i, name in enumerate(names):
+        t = arrays[name].detach()
+        dt = torch.float64 if (t.dtype == torch.float64 or not t.is_floating_point()) else torch.float32
+        isz = 8 if dt == torch.float64 else 4
+        k = min(t.numel(), budget // (len(names) - i) // isz)
+        if k == t.numel():
+            a = t.to(dt).cpu().numpy()
+        else:
+            idx = dump_index(name, t.numel(), k)
+            a = torch.take(t, torch.from_numpy(idx).to(t.device)).to(dt).cpu().numpy()
+        budget -= a.nbytes
+        out[name] = a
+    return out
 
 
 def fine_calls(counts, merged_off):
@@ -558,19 +604,22 @@ def main():
     tv_in_step = stage in ("fine", "lts", "pdra") and not a.no_tv
     TVS, W_TV, TV_EVERY = dict(sdf=0.1, smooth_grad=0.05), 0.01, 3
 
-    def one(it=None):
+    def one(it=None, full=False):
         """One step; ``it``: iteration number of a timed / warm-up step -- on every TV_EVERY-th the trainer's do_tv
-        lines (fine.py:383-400: smoothed-gradient TV value + gradient, in-place 6-neighbour TV gradient) run too."""
+        lines (fine.py:383-400: smoothed-gradient TV value + gradient, in-place 6-neighbour TV gradient) run too.
+        -> (loss, gradients); ``full``: everything the step returned (the LTS steps add their forward outputs)."""
         if tv_in_step and it is not None and it % TV_EVERY == 0:
-            return step.forward_loss_backward(batch, a.s_val, global_rays=n_rays * world if pg is not None else None,
-                                              entropy_owner=(rank == world - 1),
-                                              regularisers=dict(n_rays_global=n_rays * world, weight_tv_density=W_TV, tvs=TVS,
-                                                                dense_mode=True))[:2]
-        if stage == "finetune":                 # loss: 0.5 * mse(lin/pbr/emo, lin/pbr/emo_hat), pdra.py:1090-1093
-            return step.forward_loss_backward(batch, a.s_val)
-        # N > 1: this rank's rays are one shard of a global batch of n_rays * N rays
-        return step.forward_loss_backward(batch, a.s_val, global_rays=n_rays * world if pg is not None else None,
-                                          entropy_owner=(rank == world - 1))[:2]
+            r = step.forward_loss_backward(batch, a.s_val, global_rays=n_rays * world if pg is not None else None,
+                                           entropy_owner=(rank == world - 1),
+                                           regularisers=dict(n_rays_global=n_rays * world, weight_tv_density=W_TV, tvs=TVS,
+                                                             dense_mode=True))
+        elif stage == "finetune":               # loss: 0.5 * mse(lin/pbr/emo, lin/pbr/emo_hat), pdra.py:1090-1093
+            r = step.forward_loss_backward(batch, a.s_val)
+        else:
+            # N > 1: this rank's rays are one shard of a global batch of n_rays * N rays
+            r = step.forward_loss_backward(batch, a.s_val, global_rays=n_rays * world if pg is not None else None,
+                                           entropy_owner=(rank == world - 1))
+        return r if full else r[:2]
 
     # Warm-up = W PLAIN steps, exactly the steps that are timed afterwards (round 5: until then up to three of them were the
     # instrumented ones below -- serialised kernels, events around every launch -- which left the device in another state
@@ -585,6 +634,7 @@ def main():
     gc.freeze()
     gc.disable()
     n_prof = 0 if a.no_kernel_timing else 3
+    dump = a.dump_outputs is not None and rank == 0
     for i_ in range(a.warmup):
         one(i_)
     # timed region: exactly K steps; the fine stage's three large launches carry one event pair each (on their stream) -- which
@@ -602,7 +652,8 @@ def main():
         marks[0].record()
     t0 = time.perf_counter()
     for i_ in range(a.steps):
-        loss, _ = one(i_)
+        res = one(i_, full=dump and i_ == a.steps - 1)
+        loss = res[0]
         if a.step_times:
             marks.append(torch.cuda.Event(enable_timing=True))
             marks[-1].record()
@@ -618,6 +669,11 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if dump:                  # (read back now: the steps below reuse the buffers the gradients live in)
+        dumped = dump_sample(dump_arrays(res))
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name_, arr_ in dumped.items():
+            np.save(os.path.join(a.dump_outputs, name_ + ".npy"), arr_)
     kern = eng.timing_summary() if in_region else {}     # the bracketed launches: name -> (launches, total ms)
     eng.enable_timing(False)
     # the instrumented steps (outside W and K; every rank runs them: a step is collective when N > 1)
@@ -787,6 +843,9 @@ def main():
             # a timed step among them would have run twice
             "split_fallback_steps": int(getattr(eng, "split_fallback_steps", 0)),
         }
+        if dump:
+            out["dump_outputs"] = {"dir": a.dump_outputs, "files": len(dumped),
+                                   "mb": round(sum(v.nbytes for v in dumped.values()) / 1e6, 3)}
         if opt_ms is not None:
             out["optimizer_step"] = {"ms": opt_ms, "parameters": n_params, "kernel": "esr_adam_step (fused Adam, 28 B/param)",
                                      "hbm_gbs": n_params * 28 / (opt_ms * 1e-3) / 1e9,

@@ -159,22 +159,6 @@ def _grid_pad(step, n_grid: int) -> int:
     return n_grid
 
 
-def _warn_hw_queues(process_group):
-    """Data-parallel steps need >= 8 HIP hardware queues (see esr_nerf_amd/__init__.py); warn once when the process
-    was started with fewer -- the step still runs, with its side stream serialised behind the main one."""
-    if process_group is None:
-        return
-    try:
-        q = int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))
-    except ValueError:
-        q = 4
-    if q < 8:
-        import warnings
-        warnings.warn(f"GPU_MAX_HW_QUEUES={q}: with an RCCL communicator alive the engine's side stream shares a hardware "
-                      "queue with the main stream (weight gradients and packing serialise); export GPU_MAX_HW_QUEUES=8 "
-                      "before the process initialises HIP", RuntimeWarning, stacklevel=3)
-
-
 class _OverflowScope:
     """``eng.defer_overflow`` for the duration of ONE data-parallel step (an overflow must not raise on one rank while
     the others wait in the exchange); restored afterwards so that later non-DP uses of the same engine -- the autograd
@@ -254,7 +238,6 @@ class FineStep:
         self._flat = None
         self._sync = None
         self._sync_mode = os.environ.get("ESR_GRAD_SYNC", "auto")
-        _warn_hw_queues(process_group)
 
     # names follow state_dict / named_parameters of the renderer
     def _param_names(self):
@@ -455,7 +438,6 @@ class LtsStep:
         self._sync = None
         self._sync_mode = os.environ.get("ESR_GRAD_SYNC", "auto")
         self._pair_jobs = []
-        _warn_hw_queues(process_group)
 
     def close(self):
         """Call once after the final step (data parallel): reports a march overflow flagged by that step."""

@@ -18,7 +18,7 @@ from esr_nerf_amd.config import fine_cfg
 from esr_nerf_amd.synthetic import init_slab_model, slab_scene
 from oracle import native, ref_import
 
-# ESR_GOLDEN_OUT: write somewhere else (tests/test_golden_regen.py regenerates into a scratch directory and diffs)
+# ESR_GOLDEN_OUT: write somewhere else (a scratch directory, to diff against the committed fixtures)
 OUT = os.environ.get("ESR_GOLDEN_OUT") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                        "tests", "golden")
 
@@ -157,6 +157,7 @@ def main():
 
     ru.sample_pts_on_rays, ru.alpha2weight, ru.alpha2weight_backward = real_sample, real_a2w, real_a2w_b
     gen_host(ns)
+    gen_live(ns)
     for mask in ("full", "prune"):
         gen_lts(ns, mask)            # the "full" variant writes lts_g16_params.npz, which every later variant checks
         gen_finetune(ns, mask)
@@ -287,6 +288,108 @@ def gen_host(ns):
     np.savez_compressed(os.path.join(OUT, "host_dense_rows.npz"), **o)
     print("dense rows fixture:", {k: (tuple(v.shape) if hasattr(v, "shape") else v) for k, v in o.items() if "value" in k or "keep" in k},
           "kept", int(o["filter/keep/0"].sum()), int(o["filter/keep/1"].sum()), "world", o["scale/world_size"])
+
+
+def _sampler_data(n, seed):
+    """The inputs of the sampler fixtures (tests/test_data_ckpt.py reads them back from the fixture)."""
+    g = torch.Generator().manual_seed(seed)
+    return {"rays_o": torch.randn(n, 3, generator=g), "rgbs": torch.rand(n, 3, generator=g),
+            "em_modes": torch.randint(0, 2, (n,), generator=g)}
+
+
+def gen_live(ns):
+    """What the tests once compared against the reference imported live, stored as data so that they run without it:
+    the ray samplers' batch sequences (utils2/utils.py), CosineLR and the ray filter at far = 2.2, the fine path on an
+    unseen tiny scene, and the four cfg/app YAML trees with the model keys the reference's Python sources mention."""
+    import glob
+    import hashlib
+    import importlib
+    import json
+    import yaml
+    from esr_nerf_amd.config import AttrDict
+    ru = importlib.import_module("utils2.utils")
+    keys = ["rays_o", "rgbs", "em_modes"]
+    cfg_s = AttrDict(system=dict(device="cpu", data_preload="gpu"))
+    o = {}
+    # ---- BatchSampler: filter + shuffle, 20 batches of 16 (three epoch boundaries)
+    d = _sampler_data(103, 0)
+    for k, v in d.items():
+        o[f"bs/in/{k}"] = v.numpy()
+    torch.manual_seed(5)
+    s = ru.BatchSampler(cfg_s, {k: v.clone() for k, v in d.items()}, keys, 16)
+    s.filter(torch.arange(103) % 5 != 0)
+    s.shuffle()
+    for i in range(20):
+        for k, v in s.sample().items():
+            o[f"bs/{i}/{k}"] = v.numpy()
+    o["bs/batch_st"], o["bs/data_num"] = np.int64(s.batch_st), np.int64(s.data_num)
+    o["bs/data_idxs"], o["bs/rgbs"] = s.data_idxs.numpy(), s.data["rgbs"].numpy()
+    # ---- RayGroupManager: 30 batches of 24 (8 uncertain), regrouped at iterations 4 and 17
+    d = _sampler_data(211, 1)
+    for k, v in d.items():
+        o[f"rgm/in/{k}"] = v.numpy()
+    torch.manual_seed(3)
+    s = ru.RayGroupManager(cfg_s, {k: v.clone() for k, v in d.items()}, keys, 24, 8)
+    for it in range(30):
+        if it in (4, 17):
+            s.filter(torch.rand(s.uncert_data_num, generator=torch.Generator().manual_seed(it)) < 0.7)
+            s.shuffle()
+        for k, v in s.sample().items():
+            o[f"rgm/{it}/{k}"] = v.numpy()
+    o["rgm/uncert_data_idxs"], o["rgm/cert_data_idxs"] = s.uncert_data_idxs.numpy(), s.cert_data_idxs.numpy()
+    np.savez_compressed(os.path.join(OUT, "host_samplers.npz"), **o)
+    print("sampler fixture:", len(o), "arrays")
+
+    # ---- CosineLR from six resume points, and the ray filter of a fresh model at far = 2.2
+    o = {}
+    tr = dict(n_iters=333, warm_up_iters=50, warm_up_min_ratio=0.01, const_warm_up=False, cos_min_ratio=0.1)
+    for start in (0, 1, 49, 50, 51, 332):
+        c = ns.optimizer.CosineLR(AttrDict(app=dict(trainer=tr)), start)
+        o[f"cos/{start}/pre_post"] = np.array([c.pre_decay_factor, c.pos_decay_factor], np.float64)
+        o[f"cos/{start}/factors"] = np.array([c.decay_factor for _ in range(333 - start)], np.float64)
+    sc = slab_scene("g16", mask="prune")
+    torch.manual_seed(0)
+    np.random.seed(0)
+    ref = ns.VoxurfF(fine_cfg("cpu"), sc.near, 2.2, sc.xyz_min, sc.xyz_max, sc.mask_xyz_min, sc.mask_xyz_max,
+                     sc.mask_alpha_init, sc.mask_density, sc.s_val, sc.num_voxels)
+    g = torch.Generator().manual_seed(3)
+    ro = torch.cat([(torch.rand(500, 2, generator=g) * 2 - 1) * 1.2, torch.full((500, 1), 1.5)], -1)
+    rd = torch.cat([(torch.rand(500, 2, generator=g) * 2 - 1) * 0.5, -torch.ones(500, 1)], -1) * (0.4 + torch.rand(500, 1, generator=g))
+    o["filter/rays_o"], o["filter/rays_d"] = ro.numpy(), rd.numpy()
+    o["filter/sdf_random_init"] = np.bool_(ref.sdf_random_init)
+    o["filter/keep"] = ref.filter_training_rays_in_maskcache_sampling(ro, rd, 200).numpy()
+    np.savez_compressed(os.path.join(OUT, "host_lr_filter.npz"), **o)
+    print("lr / filter fixture: kept", int(o["filter/keep"].sum()), "of", len(ro))
+
+    # ---- the fine path on a seed / size / s_val no other fixture uses
+    cfg = fine_cfg("cpu")
+    sc = slab_scene("tiny", s_val=120.0, seed=7, n_rays=40, oblique=True)
+    torch.manual_seed(11)
+    m = ns.VoxurfF(cfg, sc.near, sc.far, sc.xyz_min, sc.xyz_max, sc.mask_xyz_min, sc.mask_xyz_max,
+                   sc.mask_alpha_init, sc.mask_density, sc.s_val, sc.num_voxels)
+    init_slab_model(m, sc, seed=5)
+    m.train()
+    b = sc.batch
+    res = m(rays_o=b["rays_o"], rays_d=b["rays_d"], viewdirs=b["viewdirs"], em_modes=b["em_modes"], s_val=sc.s_val)
+    # the parameters as digests, not data: init_slab_model sets every one of them, and the test's own model has to hash the same
+    o = {"sd_sha1/" + k: np.array(hashlib.sha1(v.detach().contiguous().numpy().tobytes()).hexdigest())
+         for k, v in m.state_dict().items()}
+    o.update({"out/" + k: v.detach().numpy().copy() for k, v in res.items() if torch.is_tensor(v)})
+    np.savez_compressed(os.path.join(OUT, "fine_tiny_s120.npz"), **o)
+    print("tiny fine fixture:", sum(k.startswith("out/") for k in o), "outputs")
+
+    # ---- the YAML trees (as data) and, per tree, the model keys that occur anywhere in the reference's Python sources
+    ref_root = ref_import.REF_ROOT
+    ref_py = "".join(open(f, errors="ignore").read() for f in glob.glob(os.path.join(ref_root, "**", "*.py"), recursive=True))
+    trees, mentioned = {}, {}
+    for name in ("coarse", "fine", "lts", "pdra"):
+        with open(os.path.join(ref_root, "cfg", "app", name + ".yaml")) as f:
+            trees[name] = yaml.safe_load(f)["app"]
+        mentioned[name] = sorted(k for k in trees[name]["model"] if k in ref_py)
+    with open(os.path.join(OUT, "reference_yaml.json"), "w") as f:
+        json.dump({"app": trees, "model_keys_in_reference_py": mentioned}, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("yaml fixture:", {k: len(v) for k, v in trees.items()})
 
 
 def lts_reference_loss(ns, results, rgbs, cfg):
@@ -638,6 +741,9 @@ if __name__ == "__main__":
         raise SystemExit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "host":
         gen_host(ref_import.load())
+        raise SystemExit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "live":
+        gen_live(ref_import.load())
         raise SystemExit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "lts_eval":
         gen_lts_eval(ref_import.load())

@@ -1,19 +1,13 @@
 """Ray samplers and checkpoint wire format: the index-based, rank-aware samplers return
-the reference's batches (checked against the imported reference classes when /root/reference is present, and
-through self-consistency otherwise); checkpoints round-trip in the reference layout."""
-import os
-import sys
-
+the reference's batches (tests/golden/host_samplers.npz: the batch sequences of the reference's own samplers,
+oracle/gen_golden.py::gen_live); checkpoints round-trip in the reference layout."""
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
+from conftest import load_npz
 from esr_nerf_amd.config import AttrDict, fine_cfg
 from esr_nerf_amd.data import BatchSampler, RayGroupManager
-
-sys.path.insert(0, ROOT)
-from oracle import ref_import  # noqa: E402
 
 KEYS = ["rays_o", "rgbs", "em_modes"]
 
@@ -28,34 +22,37 @@ def _data(n=103, seed=0):
             "em_modes": torch.randint(0, 2, (n,), generator=g)}
 
 
-def _ref_utils():
-    if not ref_import.available():
-        pytest.skip("reference tree not present")
-    ref_import.load()
-    import importlib
-    return importlib.import_module("utils2.utils")
+def _ref(prefix):
+    """The reference samplers' record: its inputs (== _data of the same size and seed) and, per batch, {key: tensor}."""
+    z = {k: torch.from_numpy(np.asarray(v)) for k, v in load_npz("host_samplers.npz").items() if k.startswith(prefix + "/")}
+    data = {k: z[f"{prefix}/in/{k}"] for k in KEYS}
+    batches = {}
+    for k, v in z.items():
+        parts = k.split("/", 2)
+        if parts[1].isdigit():
+            batches.setdefault(int(parts[1]), {})[parts[2]] = v
+    return z, data, [batches[i] for i in sorted(batches)]
 
 
 def test_batch_sampler_matches_reference_batches():
-    ru = _ref_utils()
+    z, data, a = _ref("bs")
     d = _data()
+    assert all(torch.equal(d[k], data[k]) for k in KEYS)
     mask = torch.arange(103) % 5 != 0
 
-    def run(cls, data):
-        torch.manual_seed(5)                               # both see the same global generator sequence
-        s = cls(_cfg(), data, KEYS, 16)
-        s.filter(mask)
-        s.shuffle()
-        return s, [s.sample() for _ in range(20)], s.batch_st      # crosses three epoch boundaries
-
-    ref, a, st_a = run(ru.BatchSampler, {k: v.clone() for k, v in d.items()})
-    ours, b, st_b = run(BatchSampler, d)
+    torch.manual_seed(5)                                   # the reference's sequence was drawn from the same global seed
+    ours = BatchSampler(_cfg(), d, KEYS, 16)
+    ours.filter(mask)
+    ours.shuffle()
+    b = [ours.sample() for _ in range(20)]                 # crosses three epoch boundaries
+    assert len(a) == len(b) == 20
     for x, y in zip(a, b):
+        assert set(x) == set(KEYS)
         for k in KEYS:
             assert torch.equal(x[k], y[k]), k
-    assert st_a == st_b
-    assert torch.equal(ref.data_idxs, ours.data_idxs) and ref.data_num == ours.data_num
-    assert torch.equal(ref.data["rgbs"], ours.current("rgbs"))
+    assert int(z["bs/batch_st"]) == ours.batch_st
+    assert torch.equal(z["bs/data_idxs"], ours.data_idxs) and int(z["bs/data_num"]) == ours.data_num
+    assert torch.equal(z["bs/rgbs"], ours.current("rgbs"))
     # resume: a sampler rebuilt from (batch_st, data_idxs) continues the same sequence (fine.py:220-227)
     again = BatchSampler(_cfg(), d, KEYS, 16, ours.batch_st, ours.data_idxs.clone())
     torch.manual_seed(9)
@@ -66,29 +63,26 @@ def test_batch_sampler_matches_reference_batches():
 
 
 def test_ray_group_manager_matches_reference_batches():
-    ru = _ref_utils()
+    z, data, a = _ref("rgm")
     d = _data(211, seed=1)
+    assert all(torch.equal(d[k], data[k]) for k in KEYS)
 
-    def run(cls, data):
-        torch.manual_seed(3)
-        s = cls(_cfg(), data, KEYS, 24, 8)
-        out = []
-        for it in range(30):
-            if it in (4, 17):                               # regrouping: some uncertain rays become certain
-                m = torch.rand(s.uncert_data_num, generator=torch.Generator().manual_seed(it)) < 0.7
-                s.filter(m)
-                s.shuffle()
-            out.append(s.sample())
-        return s, out
-
-    ref, a = run(ru.RayGroupManager, {k: v.clone() for k, v in d.items()})
-    ours, b = run(RayGroupManager, d)
+    torch.manual_seed(3)
+    ours = RayGroupManager(_cfg(), d, KEYS, 24, 8)
+    b = []
+    for it in range(30):
+        if it in (4, 17):                                   # regrouping: some uncertain rays become certain
+            m = torch.rand(ours.uncert_data_num, generator=torch.Generator().manual_seed(it)) < 0.7
+            ours.filter(m)
+            ours.shuffle()
+        b.append(ours.sample())
+    assert len(a) == len(b) == 30
     for it, (x, y) in enumerate(zip(a, b)):
         assert set(x) == set(y)
         for k in x:
             assert torch.equal(x[k], y[k]), (it, k)        # includes the all-False mask while the certain group is empty
-    assert torch.equal(ref.uncert_data_idxs, ours.uncert_data_idxs)
-    assert torch.equal(ref.cert_data_idxs, ours.cert_data_idxs)
+    assert torch.equal(z["rgm/uncert_data_idxs"], ours.uncert_data_idxs)
+    assert torch.equal(z["rgm/cert_data_idxs"], ours.cert_data_idxs)
 
 
 @pytest.mark.parametrize("world", [2, 3])

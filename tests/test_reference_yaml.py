@@ -1,25 +1,26 @@
 """B1's "drops into run.py under the existing Hydra configs", pinned: the reference's ACTUAL YAML tree
-(/root/reference/cfg/app/{coarse,fine,lts,pdra}.yaml, read as data) against what esr_nerf_amd/config.py restates by hand
-for tests and bench.py, and the three renderers constructed from the loaded ``app.model`` trees.  Build-container only:
-/root/reference does not exist on the GPU box (skipped there); nothing of the reference is imported or executed."""
+(cfg/app/{coarse,fine,lts,pdra}.yaml, stored as data in tests/golden/reference_yaml.json by oracle/gen_golden.py::gen_live)
+against what esr_nerf_amd/config.py restates by hand for tests and bench.py, and the three renderers constructed from the
+loaded ``app.model`` trees."""
+import json
 import os
 
 import numpy as np
 import pytest
 import torch
-import yaml
 
-CFG = "/root/reference/cfg/app"
-pytestmark = pytest.mark.skipif(not os.path.isdir(CFG), reason="the reference tree is not on this machine")
+from conftest import GOLDEN
+
+with open(os.path.join(GOLDEN, "reference_yaml.json")) as _f:
+    REF = json.load(_f)
 
 
 def _load(name):
-    with open(os.path.join(CFG, name + ".yaml")) as f:
-        return yaml.safe_load(f)["app"]
+    return REF["app"][name]
 
 
 def _same(a, b):
-    """YAML 1.1 (PyYAML) reads ``1e-5`` as a string where OmegaConf reads a float: numbers compare as numbers."""
+    """YAML 1.1 (PyYAML, which wrote the fixture) reads ``1e-5`` as a string where OmegaConf reads a float: numbers compare as numbers."""
     if isinstance(b, dict):
         return isinstance(a, dict) and all(k in a and _same(a[k], v) for k, v in b.items())
     if isinstance(b, (list, tuple)):
@@ -112,8 +113,8 @@ def test_renderers_construct_from_the_references_model_tree(yaml_name, cls):
     assert sum(p.numel() for p in m.parameters()) > 0
     unread = set(model_tree) - model_tree.read
     # A key of the tree the constructor never looked at would be a setting silently ignored -- unless the reference ignores
-    # it too (pdra.yaml:41 `ray_sampling_eval` occurs in no .py file of the reference; its sources are read as text here)
-    import glob
-    ref_py = "".join(open(f, errors="ignore").read() for f in glob.glob("/root/reference/**/*.py", recursive=True))
-    ignored_here_only = sorted(k for k in unread if k in ref_py)
+    # it too (pdra.yaml:41 `ray_sampling_eval` occurs in no .py file of the reference; the fixture lists, per tree, the
+    # model keys that occur as text anywhere in the reference's Python sources)
+    mentioned = set(REF["model_keys_in_reference_py"][yaml_name])
+    ignored_here_only = sorted(k for k in unread if k in mentioned)
     assert not ignored_here_only, (yaml_name, cls, ignored_here_only)

@@ -6,7 +6,6 @@ TAG=${1:-d}; shift
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
-export GPU_MAX_HW_QUEUES=8
 STEPS=10; WARM=3
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --output-format csv -d "$OUT/${TAG}_trace" -o run -- python3 "$ROOT/bench.py" --steps $STEPS --warmup $WARM --no-cpu-baseline --no-optimizer --no-kernel-timing --serial --no-other "$@" > "$OUT/${TAG}_trace.log" 2>&1

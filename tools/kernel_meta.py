@@ -20,7 +20,9 @@ EXTRA = _build_extra()     # per-source flags, as esr_nerf_amd/build.py
 
 def asm_of(src, out=None, extra=()):
     extra = tuple(extra) + EXTRA.get(os.path.basename(src), ())
-    out = out or os.path.join("/tmp", "esr_asm_" + os.path.basename(src) + ".s")
+    if out is None:           # beside the library's objects: per checkout, never a file another user of the machine owns
+        out = os.path.join(ROOT, "esr_nerf_amd", "_obj", "asm_" + os.path.basename(src) + ".s")
+        os.makedirs(os.path.dirname(out), exist_ok=True)
     stamp = out + ".stamp"
     deps = [src] + glob.glob(os.path.join(os.path.dirname(src), "*.h")) + [os.path.join(ROOT, "include", "esr_hip.h")]
     key = str([(d, os.path.getmtime(d)) for d in deps]) + str(extra) + str(FLAGS)

@@ -4,7 +4,6 @@
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 ARGS=${*:---config C5}
 cd /tmp && export TMPDIR=/tmp
-export GPU_MAX_HW_QUEUES=8
 rm -rf "$ROOT/gpurun_out/tr_lts"
 rocprofv3 --kernel-trace --output-format csv -d "$ROOT/gpurun_out/tr_lts" -o run -- python3 "$ROOT/bench.py" $ARGS --steps 6 --warmup 4 --no-cpu-baseline --no-kernel-timing --no-optimizer > "$ROOT/gpurun_out/tr_lts.log" 2>&1
 cd "$ROOT" && python3 - <<'PY'
