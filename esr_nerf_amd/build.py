@@ -1,14 +1,23 @@
-"""Build libesr_hip.so (in-tree) with hipcc for gfx950.
+"""Build libesr_hip.so (in-tree) with hipcc for gfx950; the one owner of the compile command.
 
-``python -m esr_nerf_amd.build`` or ``__graft_entry__.build()``.  hipcc
-cross-compiles without a GPU; the built library travels to the GPU box with the
-repo snapshot (it is git-ignored, not gpurun-ignored).
+``python -m esr_nerf_amd.build [--force]`` or ``__graft_entry__.build()``.  hipcc
+cross-compiles without a GPU; the built library is git-ignored.  Everything else that
+compiles a product source uses ``hipcc_cmd`` (the product's flags for that source):
+
+    python -m esr_nerf_amd.build --variant NAME SRC [FLAG ...]   tools/_variants/NAME.so: the in-tree library with
+                                                                 csrc/SRC recompiled under the additional flags (an A/B
+                                                                 build, loaded with ESR_LIB_PATH)
+    python -m esr_nerf_amd.build --flags SRC                     the product's flags for csrc/SRC (for harnesses that
+                                                                 #include it: tools/ubench/build.sh)
+    device_asm(SRC)                                              device assembly of csrc/SRC (tools/kernel_meta.py,
+                                                                 tools/isa_waits.py, tests/test_isa.py)
 """
 from __future__ import annotations
 
 import concurrent.futures as cf
 import hashlib
 import os
+import shlex
 import subprocess
 import sys
 
@@ -16,6 +25,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libesr_hip.so")
+HEADER = os.path.join(os.path.dirname(HERE), "include", "esr_hip.h")
+VARIANTS = os.path.join(os.path.dirname(HERE), "tools", "_variants")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 # NO packed-fp32 arithmetic (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32 / v_pk_mov_b32) in any product kernel: the target feature is
@@ -23,8 +34,9 @@ ARCH = "gfx950"
 # vectoriser, a sum of two f32x4 accumulators in the source -- is scalarised by the backend.
 # Why (round 6, DESIGN 5 "packed fp32"): on this hardware a packed-fp32 instruction whose op_sel reads a HIGH half for the low result
 # (v_pk_add_f32 / v_pk_mul_f32 ... op_sel:[0,1]) returns wrong results in lanes 48-63 while ANOTHER wave of the same SIMD alternates
-# MFMAs with op_sel'd v_fma_mix_f32 -- which is what the split-fp16 kernels do.  tools/ubench/pk_beside_mfma.hip shows it with nothing
-# of this library involved (6.9 M wrong results in 3000 launches, none in any other lane quarter, none beside any other load);
+# MFMAs with op_sel'd v_fma_mix_f32 -- which is what the split-fp16 kernels do.  A standalone kernel showed it with nothing of
+# this library involved (6.9 M wrong results in 3000 launches, none in any other lane quarter, none beside any other load:
+# profiles/r06_pk_beside_mfma.txt);
 # esr_expgrad_fwd, whose x / y interpolation weights the SLP vectoriser had packed exactly so, returned wrong rows in 44 % of its
 # launches beside the C2 step and in 1.5 % of the light-transport steps of two ranks sharing a card (profiles/r06_packed_fp32_lanes.txt).
 # Cost: none -- three builds alternating on one box, C2 step: packed 2.066-2.083 ms, this build 2.053-2.070 ms, this build without
@@ -34,21 +46,6 @@ ARCH = "gfx950"
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function", "-fno-fast-math", *NO_PACKED_FP32]
-FLAGS += os.environ.get("ESR_EXTRA_HIPCC_FLAGS", "").split()      # developer experiments (-DESR_EXP_...), build time only
-
-
-def _sources():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
-
-
-def _stamp(paths):
-    h = hashlib.sha1()
-    for p in sorted(paths):
-        with open(p, "rb") as f:
-            h.update(f.read())
-    h.update(" ".join(FLAGS).encode())
-    h.update(repr(sorted(EXTRA.items())).encode())
-    return h.hexdigest()
 
 
 # per-source flags.
@@ -64,26 +61,49 @@ def _stamp(paths):
 EXTRA = {"tone_wgrad.hip": ["-fno-slp-vectorize"], "mlp_split.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 
-def _compile(src):
-    obj = os.path.join(OBJ, src[:-4] + ".o")
-    deps = [os.path.join(CSRC, src)] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    deps.append(os.path.join(os.path.dirname(HERE), "include", "esr_hip.h"))
-    stamp = _stamp(deps)
-    sfile = obj + ".stamp"
-    if os.path.exists(obj) and os.path.exists(sfile) and open(sfile).read() == stamp:
-        return obj, False
-    cmd = [HIPCC, *FLAGS, *EXTRA.get(src, []), "-c", os.path.join(CSRC, src), "-o", obj]
-    r = subprocess.run(cmd, capture_output=True, text=True)
+def hipcc_cmd(src, extra=()):
+    """hipcc with the product's flags for csrc/SRC (FLAGS + EXTRA[src]), then the caller's additional flags."""
+    return [HIPCC, *FLAGS, *EXTRA.get(src, []), *extra]
+
+
+def sources():
+    return sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
+
+
+def _make(src, out, args):
+    """Compile csrc/SRC into `out` with the product's flags + `args`, unless out's stamp shows it was built from these sources
+    with these flags (paths are left out of the stamp: a moved checkout stays built).  Returns whether it compiled."""
+    h = hashlib.sha1(" ".join(hipcc_cmd(src, args)[1:]).encode())
+    for p in sorted([os.path.join(CSRC, src), HEADER] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]):
+        with open(p, "rb") as f:
+            h.update(f.read())
+    stamp, sfile = h.hexdigest(), out + ".stamp"
+    if os.path.exists(out) and os.path.exists(sfile) and open(sfile).read() == stamp:
+        return False
+    r = subprocess.run([*hipcc_cmd(src, args), os.path.join(CSRC, src), "-o", out], capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"hipcc failed for {src}:\n{r.stdout}\n{r.stderr}")
     # (the host pass of the same command does not know the device feature: "'-packed-fp32-ops' is not a recognized feature for
-    #  this target (ignoring feature)", once per function -- dropped; everything else the compiler says is passed on)
-    err = "\n".join(l for l in r.stderr.splitlines() if "'-packed-fp32-ops' is not a recognized feature" not in l)
+    #  this target (ignoring feature)", once per function; hipcc's own '--hip-link' is unused by a -S compile -- both dropped;
+    #  everything else the compiler says is passed on)
+    noise = ("'-packed-fp32-ops' is not a recognized feature", "argument unused during compilation: '--hip-link'")
+    err = "\n".join(l for l in r.stderr.splitlines() if not any(n in l for n in noise))
     if err.strip():
         sys.stderr.write(err + "\n")
     with open(sfile, "w") as f:
         f.write(stamp)
-    return obj, True
+    return True
+
+
+def _compile(src, extra=(), obj=None):
+    obj = obj or os.path.join(OBJ, src[:-4] + ".o")
+    return obj, _make(src, obj, [*extra, "-c"])
+
+
+def _link(objs, lib):
+    r = subprocess.run([HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", lib, *objs], capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
 
 
 def build_lib(force: bool = False, jobs: int = 4) -> str:
@@ -91,17 +111,40 @@ def build_lib(force: bool = False, jobs: int = 4) -> str:
     if force:
         for f in os.listdir(OBJ):
             os.remove(os.path.join(OBJ, f))
-    srcs = _sources()
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:
-        res = list(ex.map(_compile, srcs))
-    objs = [o for o, _ in res]
+        res = list(ex.map(_compile, sources()))
     if any(changed for _, changed in res) or not os.path.exists(LIB):
-        cmd = [HIPCC, "-shared", "-fPIC", f"--offload-arch={ARCH}", "-o", LIB, *objs]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+        _link([o for o, _ in res], LIB)
     return LIB
 
 
+def build_variant(name, src, extra=()) -> str:
+    """tools/_variants/NAME.so: the in-tree objects with csrc/SRC recompiled (into NAME.o) under the additional flags."""
+    if src not in sources():
+        raise ValueError(f"no source csrc/{src}")
+    build_lib()
+    os.makedirs(VARIANTS, exist_ok=True)
+    obj, _ = _compile(src, extra, os.path.join(VARIANTS, name + ".o"))
+    lib = os.path.join(VARIANTS, name + ".so")
+    _link([obj if s == src else os.path.join(OBJ, s[:-4] + ".o") for s in sources()], lib)
+    return lib
+
+
+def device_asm(src) -> str:
+    """Device assembly of csrc/SRC as the product compiles it: esr_nerf_amd/_obj/<name>.s for <name>.hip."""
+    os.makedirs(OBJ, exist_ok=True)
+    out = os.path.join(OBJ, src[:-4] + ".s")
+    _make(src, out, ["-S", "--cuda-device-only"])
+    return out
+
+
 if __name__ == "__main__":
-    print(build_lib(force="--force" in sys.argv))
+    args = sys.argv[1:]
+    if args[:1] == ["--variant"] and len(args) >= 3:
+        print(build_variant(args[1], args[2], args[3:]))
+    elif args[:1] == ["--flags"] and len(args) == 2:
+        print(shlex.join(hipcc_cmd(args[1])[1:]))
+    elif args in ([], ["--force"]):
+        print(build_lib(force=bool(args)))
+    else:
+        sys.exit(__doc__)

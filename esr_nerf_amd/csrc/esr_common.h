@@ -140,11 +140,7 @@ __device__ __forceinline__ RayGeom esr_ray_geom(const float *rays_o, const float
 // two separate calls were most of the feature kernel's vector instructions
 __device__ __forceinline__ void esr_sincos(float a, float &s, float &c)
 {
-#ifdef ESR_EXP_SEPARATE_SINCOS
-    s = sinf(a); c = cosf(a);
-#else
     sincosf(a, &s, &c);
-#endif
 }
 
 struct Tri {
@@ -272,9 +268,7 @@ static __device__ __forceinline__ float esr_readlane(float x, int i)
     return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(x), i));
 }
 
-#ifndef ESR_NT_AUX
 #define ESR_NT_AUX 2          // gfx940+ buffer cache-policy bits: 1 = sc0, 2 = nt, 16 = sc1
-#endif
 // Buffer addressing for every hot kernel's tile traffic.  Besides the addressing economy described below, buffer STORES
 // retire much faster than plain global stores here: a wave's later loads wait for its earlier stores (vmcnt retires in
 // order and counts stores), and 6 `global_store_dword` per tile at the end of the MLP input-gradient kernel cost 31 us

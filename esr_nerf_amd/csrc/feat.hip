@@ -665,7 +665,7 @@ __global__ void __launch_bounds__(256, 2) feat_bwd_kernel(FeatParams P)
         // Gradient rows of this sample, summed over the nets that consumed the tile (rows 6-42 are shared), and the saved
         // normals: ALL of a tile's loads are issued here, before anything waits.  (They used to be fetched where they are
         // used, behind wave-uniform branches: ~60 load -> wait round trips per tile were 0.08 of this kernel's 0.29 ms at
-        // C2 -- tools/variant.sh with the loads replaced by constants.)  Lane half h needs the rows of its two bars only.
+        // C2 -- a variant build with the loads replaced by constants.)  Lane half h needs the rows of its two bars only.
         int nact = 0, k_one = 0;
 #pragma unroll
         for (int k = 0; k < MAX_SRC; ++k)
@@ -978,9 +978,6 @@ ESR_API int esr_fine_feat_fwd(const esr_scene_t *scene, const esr_feat_args_t *a
     P.X = X; P.gnorm = gnorm;
     bool bar = true;                                    // every stencil radius within the bar's reach?
     for (int k = 0; k < 4; ++k) bar = bar && scene->grad_feat[k] >= 0.f && scene->grad_feat[k] <= BAR_MAX_DISP;
-#ifdef ESR_FEAT_DIRECT
-    bar = false;                                        // developer build: the direct form, for bit comparisons
-#endif
     const int grid = esr_grid_for((int64_t)P.tiles_all * 32, 256, 256 * 16);
     if (bar) feat_fwd_kernel<true><<<grid, 256, 0, esr_stream(stream)>>>(P);
     else feat_fwd_kernel<false><<<grid, 256, 0, esr_stream(stream)>>>(P);

@@ -31,15 +31,6 @@
 
 #include "mlp_common.h"
 
-// In-kernel time stamps: nothing in the product build; tools/ubench/fwd_stamps.hip defines ESR_STAMP before including
-// this file to record s_memtime at the layer seams of one traced wave per SIMD.
-#ifndef ESR_DSTAMP
-#define ESR_DSTAMP(i)
-#endif
-#ifndef ESR_STAMP
-#define ESR_STAMP(i)
-#endif
-
 namespace {
 
 struct FwdArgs {
@@ -99,7 +90,6 @@ __global__ void __launch_bounds__(256, 2) mlp_fwd_kernel(FwdArgs A)
         const int sv = second ? A.save2 : det ? 0 : A.save;  // 1: hidden tiles + ReLU masks, 2: masks only
         const bool save = sv != 0;
         float *const zdst = second ? A.zout2 : A.zout;
-        ESR_STAMP(0);
         float B1[KP1];
 #pragma unroll
         for (int p = 0; p < KP1; ++p)
@@ -111,7 +101,6 @@ __global__ void __launch_bounds__(256, 2) mlp_fwd_kernel(FwdArgs A)
         load_bias<HT>(W, (int)L.off_bf[0] * 4, acc2[0], lane);
         StreamPre pre = stream_prefetch<HT * (KP1 / 4)>(W, (int)L.off_wf[0] * 4, lane);
         stream_layer_pre<KP1 / 4, HT>(W, (int)L.off_wf[0] * 4, pre, [&](int k) { return B1[k]; }, acc2[0], lane);
-        ESR_STAMP(1);
         f32x4 z4[NP4];
         float bias4[D.zrows];
 #pragma unroll
@@ -133,13 +122,11 @@ __global__ void __launch_bounds__(256, 2) mlp_fwd_kernel(FwdArgs A)
                 store_relu_mask<HT>(make_rsrc(A.M[l] + (size_t)t * (MBYTES / 4), MBYTES), cur, lane);
             }
             __builtin_amdgcn_s_setprio(0);
-            ESR_STAMP(2 + 2 * l);
             if (l + 1 < NHID)
                 stream_layer_pre<HT * 4, HT>(W, (int)L.off_wf[l + 1] * 4, pre,
                                              [&](int k) { return cur[k >> 4][k & 15]; }, nxt, lane);
             else
                 lds4_layer<HT, NP4>(w4, cur, z4, lane);
-            ESR_STAMP(3 + 2 * l);
         }
         // each half of the wave holds the sum over ITS 16*HT units: add the halves, then the bias (rows >= out_dim
         // have zero weights and bias: the padding row of the output tile is written as 0)
@@ -185,7 +172,6 @@ __global__ void __launch_bounds__(256, mlp_occ(KIND)) mlp_dgrad_kernel(DgradArgs
         const bool second = A.packed2 && t >= A.t_split;         // wave-uniform
         const rsrc_t W = second ? W2 : W1;
         const float4 *wx4 = wx4s + (second ? NWX : 0);
-        ESR_DSTAMP(0);
         const rsrc_t RZ = make_rsrc(A.dz + (size_t)t * D.zrows * 32, D.zrows * 32 * 4);
         float B0[4];                                                         // pair p <-> rows 2p, 2p+1
 #pragma unroll
@@ -197,40 +183,32 @@ __global__ void __launch_bounds__(256, mlp_occ(KIND)) mlp_dgrad_kernel(DgradArgs
         f32x16 cur[HT];
         zero_tiles<HT>(cur);
         layer_from_regs<4, HT>(W, (int)L.off_wb[NHID] * 4, B0, cur, lane);
-        ESR_DSTAMP(1);
         __builtin_amdgcn_s_setprio(3);
         apply_relu_mask<HT>(msk[NHID - 1], cur);
         if (A.dZ[NHID - 1]) store_tiles<HT>(make_rsrc(A.dZ[NHID - 1] + (size_t)t * (HBYTES / 4), HBYTES), cur, lane);
         __builtin_amdgcn_s_setprio(0);
-        ESR_DSTAMP(2);
 #pragma unroll
         for (int l = NHID - 1; l >= 1; --l) {
             f32x16 nxt[HT];
             zero_tiles<HT>(nxt);
             layer_from_acc<HT, HT>(W, (int)L.off_wb[l] * 4, cur, nxt, lane);
-            ESR_DSTAMP(3 + 2 * (NHID - 1 - l));
             __builtin_amdgcn_s_setprio(3);
             apply_relu_mask<HT>(msk[l - 1], nxt);
             if (A.dZ[l - 1]) store_tiles<HT>(make_rsrc(A.dZ[l - 1] + (size_t)t * (HBYTES / 4), HBYTES), nxt, lane);
             __builtin_amdgcn_s_setprio(0);
 #pragma unroll
             for (int it = 0; it < HT; ++it) cur[it] = nxt[it];
-            ESR_DSTAMP(4 + 2 * (NHID - 1 - l));
         }
         // rows 0-31 as a 32x32 tile; the rows above that still lead to a grid (dx_rows) as 4-row 4x4x1 passes: a
         // second 32x32 tile would spend 96 MFMAs on 1 (tone mapper) to 11 (sample nets) useful rows
         f32x16 dx[1];
         zero_tiles<1>(dx);
         layer_from_acc<HT, 1>(W, (int)L.off_wb[0] * 4, cur, dx, lane);
-        ESR_DSTAMP(7);
         store_tiles<1, false>(make_rsrc(A.dX + (size_t)t * 64 * 32, 64 * 32 * 4), dx, lane);    // (the scatter reads dX next)
-        ESR_DSTAMP(8);
         if constexpr (NPX > 0) {
             f32x4 x4[NPX];
             lds4_layer<HT, NPX>(wx4, cur, x4, lane);
-            ESR_DSTAMP(9);
             store_rows4<NPX, false, false>(make_rsrc(A.dX + (size_t)t * 64 * 32, 64 * 32 * 4), 32, x4, nullptr, lane);
-            ESR_DSTAMP(10);
         }
     }
 }
@@ -259,12 +237,9 @@ struct WgradArgs {
 // (256 x 147 KB written, then read by the reduction) and the ring has to fill and drain.  With J jobs per launch each
 // job runs on 256/J workgroups: J times fewer, J times longer launches, and J times less slab traffic per layer.
 // (16 since the end of round 4: the sixteen radiance jobs of an LTS flush -- two nets x four layers x two passes -- are one
-//  launch; C5 2.97 -> 2.91 ms, C4 unchanged, A/B on one box with tools/variant.sh -DESR_MAX_JOBS=8.  The batch is a kernel
-//  argument: 16 x 152 B, inside the 4 KB limit.)
-#ifndef ESR_MAX_JOBS
-#define ESR_MAX_JOBS 16
-#endif
-constexpr int MAX_JOBS = ESR_MAX_JOBS;
+//  launch; C5 2.97 -> 2.91 ms, C4 unchanged, A/B on one box against 8: docs/history.md section 10, row 23.  The batch is a
+//  kernel argument: 16 x 152 B, inside the 4 KB limit.)
+constexpr int MAX_JOBS = 16;
 struct WgradBatch {
     int n;
     WgradArgs job[MAX_JOBS];
@@ -1353,15 +1328,7 @@ ESR_API int esr_mlp_dgrad_fine(const float *packed_emo, const float *packed_off,
 ESR_API int esr_mlp_dgrad(int kind, const float *packed, const float *dz, int32_t t0, int32_t t1,
                           const uint32_t *const *M, float *const *dZ, float *dX, void *stream)
 {
-    return esr_mlp_dgrad_wg(kind, packed, dz, t0, t1, M, dZ, dX, 0, stream);
-}
-
-// max_workgroups > 0 caps the grid (256 = one 4-wave workgroup per CU: half the register file and all of the LDS stay
-// free for a latency-bound kernel of another stream -- the grid scatters -- to run beside the matrix work).
-ESR_API int esr_mlp_dgrad_wg(int kind, const float *packed, const float *dz, int32_t t0, int32_t t1,
-                             const uint32_t *const *M, float *const *dZ, float *dX, int32_t max_workgroups, void *stream)
-{
-    if (!kind_ok(kind) || t0 < 0 || t1 < t0 || max_workgroups < 0) return ESR_EINVAL;
+    if (!kind_ok(kind) || t0 < 0 || t1 < t0) return ESR_EINVAL;
     if (t1 == t0) return 0;
     if (!packed || !dz || !M || !dZ || !dX) return ESR_EINVAL;
     const int nhid = net_desc(kind).n_layers - 1;
@@ -1371,8 +1338,7 @@ ESR_API int esr_mlp_dgrad_wg(int kind, const float *packed, const float *dz, int
         if (!M[l]) return ESR_EINVAL;
         A.M[l] = M[l]; A.dZ[l] = dZ[l];      // a NULL dZ[l] is not stored (its weight gradient recomputes it)
     }
-    int grid = mlp_grid(t1 - t0, mlp_occ(kind));
-    if (max_workgroups > 0 && grid > max_workgroups) grid = max_workgroups;
+    const int grid = mlp_grid(t1 - t0, mlp_occ(kind));
     hipStream_t s = esr_stream(stream);
     switch (kind) {
     case ESR_MLP_RADIANCE: mlp_dgrad_kernel<ESR_MLP_RADIANCE><<<grid, 256, 0, s>>>(A); break;

@@ -47,13 +47,8 @@ namespace {
 
 constexpr int SPW = 4;                                      // waves per workgroup = tiles per group
 constexpr float SPLIT_RANGE = 60000.f;                      // hidden activations at or above this raise the range flag (fp16 ends at 65504)
-#ifndef ESR_SPLIT_WRING
-#define ESR_SPLIT_WRING 3
-#endif
-constexpr int WRING = ESR_SPLIT_WRING;
-#ifndef ESR_NS_DEFAULT
-#define ESR_NS_DEFAULT 0                                    // esr_mlp_split_variant's initial value
-#endif                      // k-steps of weight operands in flight per wave (tools/ubench/split_stamps.hip: 3 / 4 / 5 / 6)
+constexpr int WRING = 3;                                    // k-steps of weight operands in flight per wave (4 / 5 / 6: no faster,
+                                                            //  docs/history.md section 10)
 
 __device__ __forceinline__ f32x16 mfma_h(f16x8 a, f16x8 b, f32x16 c)
 {
@@ -344,21 +339,9 @@ __global__ void __launch_bounds__(64 * SPW, split_occ(KIND)) mlp_fwd_split_kerne
                 // sank to the kernel's end and kept every value alive; operands are the integer max's VALU results)
                 asm volatile("v_max3_i32 %0, %0, %1, %2" : "+v"(rmax) : "v"(__float_as_int(v0)), "v"(__float_as_int(v1)));
                 const rsrc_t RH = make_rsrc(AB.H[l] + (size_t)t * (HBYTES / 4), hrec);      // fp32 tile, mlp.hip's store_tiles order
-#if defined(ESR_SPLIT_H24)
-                // timing variant (tools/ubench/split_stamps_h24: what would a 3-byte tile format cost / return in THIS kernel?):
-                // the top 24 bits of a row pair's two values as one dword + one short store (wrong layout, right byte count)
-                asm volatile("" : "+v"(hv));
-                {
-                    const unsigned u0 = __float_as_uint(v0), u1 = __float_as_uint(v1);
-                    const unsigned hi2 = __builtin_amdgcn_perm(u1, u0, 0x07060302u), mid2 = __builtin_amdgcn_perm(u1, u0, 0x0c0c0501u);
-                    bstore1_nt(RH, __uint_as_float(hi2), hv + tile_soff(0, r0), it * 4096);
-                    __builtin_amdgcn_raw_buffer_store_b16((unsigned short)mid2, RH, hv + tile_soff(0, r0 + 1), it * 4096, ESR_NT_AUX);
-                }
-#elif !defined(ESR_SPLIT_NO_HSTORE)
                 asm volatile("" : "+v"(hv));                       // (opaque per slice: a shared `hv + row offset` is kept in a
                 bstore1_nt(RH, v0, hv + tile_soff(0, r0), it * 4096);       //  register of its own instead of the store's immediate)
                 bstore1_nt(RH, v1, hv + tile_soff(0, r0 + 1), it * 4096);
-#endif
                 ev[r0] = v0; ev[r0 + 1] = v1;
             } else if constexpr (q == 1) {
                 const float v0 = ev[r0], v1 = ev[r0 + 1];
@@ -419,15 +402,11 @@ __global__ void __launch_bounds__(64 * SPW, split_occ(KIND)) mlp_fwd_split_kerne
                 });
                 sfor<0, NTOT>([&](auto NC) {
                     constexpr int n = decltype(NC)::value, tt_ = n / KS, j = n % KS, it = 2 * p + tt_;
-#ifndef ESR_SPLIT_NO_WREAD
                     if constexpr (n + WR - 1 < NTOT) {
                         constexpr int t2 = (n + WR - 1) / KS, j2 = (n + WR - 1) % KS;
                         wb[(n + WR - 1) % WR][0] = mine[((t2 * 2 + 0) * KS + j2) * 64];
                         wb[(n + WR - 1) % WR][1] = mine[((t2 * 2 + 1) * KS + j2) * 64];
                     }
-#else
-                    if constexpr (n == 0 && NTOT >= WR) { wb[WR - 1][0] = mine[(WR - 1) * 64]; wb[WR - 1][1] = mine[(KS + WR - 1) * 64]; }
-#endif
                     if constexpr (j == 0 && !LAST && PREFETCH_X) { // this tile's biases, for its epilogue a tile from now
                         const float4 *bp = reinterpret_cast<const float4 *>(bias_l + l * S::BIAS_FLOATS + it * 32 + (lane >> 5) * 16);
 #pragma unroll
@@ -458,13 +437,6 @@ __global__ void __launch_bounds__(64 * SPW, split_occ(KIND)) mlp_fwd_split_kerne
                         }
                         __builtin_amdgcn_sched_barrier(0);         // one MFMA + its micro-slice per scheduling region
                     };
-#ifdef ESR_SPLIT_NO_MFMA                                           // (timing variants of tools/ubench/split_stamps.hip: wrong results)
-                    if (j == 0) m = zero16;
-                    m[j & 15] += (float)(w1[0] + in2[j][0]) + (float)(w2[0] + in1[j][0]);
-                    ride(std::integral_constant<int, 3 * j + 0>{});
-                    ride(std::integral_constant<int, 3 * j + 1>{});
-                    ride(std::integral_constant<int, 3 * j + 2>{});
-#else
                     // (three dependent MFMAs in a row: behind a micro-slice the predecessor has long finished; in the
                     //  slots without one the dependent issue costs a few clocks -- tools/ubench/mfma_valu_overlap.hip)
                     m = mfma_h(w1, in2[j], j == 0 ? zero16 : m);
@@ -473,7 +445,6 @@ __global__ void __launch_bounds__(64 * SPW, split_occ(KIND)) mlp_fwd_split_kerne
                     ride(std::integral_constant<int, 3 * j + 1>{});
                     m = mfma_h(w2, in1[j], m);
                     ride(std::integral_constant<int, 3 * j + 2>{});
-#endif
                 });
                 if constexpr (LAST) {
                     const float4 bz = *reinterpret_cast<const float4 *>(bias_l + l * S::BIAS_FLOATS + (lane >> 5) * 16);

@@ -576,15 +576,6 @@ ESR_API int esr_fine_loss_fwd_bwd_dp(const float *srgb_marched, const float *lin
     return 0;
 }
 
-ESR_API int esr_fine_loss_fwd_bwd(const float *srgb_marched, const float *lin_marched,
-                                  const float *alphainv_last, const float *rgbs, int32_t n_rays,
-                                  float white_bg, float weight_linear, float weight_entropy_last,
-                                  float *loss, float *g_srgb, float *g_lin, float *g_last, void *stream)
-{
-    return esr_fine_loss_fwd_bwd_dp(srgb_marched, lin_marched, alphainv_last, rgbs, n_rays, white_bg, weight_linear,
-                                    weight_entropy_last, 1.f, loss, g_srgb, g_lin, g_last, stream);
-}
-
 ESR_API int esr_eval_aux(const float *X, int32_t xrows, int32_t row_nx, int32_t row_ny, int32_t row_nz,
                          const int32_t *rec_ray, const int32_t *rec_step, int32_t tiles,
                          const float *pos_rt_host, float stepdist, float *aux, void *stream)

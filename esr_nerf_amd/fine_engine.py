@@ -104,7 +104,7 @@ class _Workspace:
 
 # (module-level classes: a class defined inside the method that returns it is a new TYPE per call -- a type is a reference
 #  cycle of its own, its methods' closures held the engine, and the engine's workspaces then lived until Python's cycle
-#  collector ran: tools/debug/cycle_probe.py)
+#  collector ran: docs/history.md section 11, row 7)
 class _F32Only:
     def __init__(self, eng):
         self.eng = eng

@@ -47,7 +47,7 @@ class Pass:
     def ensure(self, tiles):
         # headroom from the FIRST allocation on: the tile counts of the light-transport passes move by +-15 % from step to step
         # (random surface points and directions), and a step that exceeds the capacity reallocates every buffer of the pass --
-        # 12 hipMalloc calls, 82 ms, once (tools/debug/alloc_per_step.py: step 6 of a C5 run, in the middle of a short bench run)
+        # 12 hipMalloc calls, 82 ms, once (step 6 of a C5 run, in the middle of a short bench run: docs/history.md, round 6 summary)
         if tiles > self.cap:
             self.cap = int(max(tiles, self.cap) * 1.25) + 16
             self.bufs = {}

@@ -37,7 +37,8 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-int esr_abi_version(void);          /* bumps whenever a signature below changes */
+#define ESR_ABI_VERSION 26
+int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
 /* ------------------------------------------------------------------------- *
@@ -479,10 +480,6 @@ int esr_mlp_dgrad_fine_bf16(const void *packed16_emo, const void *packed16_off, 
  */
 int esr_mlp_dgrad(int kind, const float *packed, const float *dz, int32_t t0, int32_t t1,
                   const uint32_t *const *M, float *const *dZ, float *dX, void *stream);
-/* The same with the grid capped at max_workgroups (0 = no cap; 256 = one workgroup per CU, which leaves half of the
- * register file and the LDS to a latency-bound kernel enqueued on another stream). */
-int esr_mlp_dgrad_wg(int kind, const float *packed, const float *dz, int32_t t0, int32_t t1,
-                     const uint32_t *const *M, float *const *dZ, float *dX, int32_t max_workgroups, void *stream);
 
 /*
  * Weight/bias gradients accumulated into the reference-layout tensors gw[l] [out,in],
@@ -603,15 +600,11 @@ int esr_fine_tone_in_bwd(const float *dXt, const float *Xt, const float *g_lin, 
 /*
  * Trainer-step loss of the fine stage (app/fine/fine.py:355-382) and its
  * gradient w.r.t. the three renderer outputs, one launch.  loss [1] f32 is
- * accumulated into (caller zero-fills).
+ * accumulated into (caller zero-fills).  Every term (loss and gradients) is
+ * multiplied by `scale`: 1, or a rank's share n_local / n_global of a
+ * data-parallel batch, whose mean-reduced terms are means over the GLOBAL
+ * batch (no reference counterpart).
  */
-int esr_fine_loss_fwd_bwd(const float *srgb_marched, const float *lin_marched,
-                          const float *alphainv_last, const float *rgbs, int32_t n_rays,
-                          float white_bg, float weight_linear, float weight_entropy_last,
-                          float *loss, float *g_srgb, float *g_lin, float *g_last,
-                          void *stream);
-/* The same with every term (loss and gradients) multiplied by `scale`: a rank's share n_local / n_global of a
- * data-parallel batch, whose mean-reduced terms are means over the GLOBAL batch (no reference counterpart). */
 int esr_fine_loss_fwd_bwd_dp(const float *srgb_marched, const float *lin_marched,
                              const float *alphainv_last, const float *rgbs, int32_t n_rays,
                              float white_bg, float weight_linear, float weight_entropy_last, float scale,

@@ -158,7 +158,7 @@ def test_split_kernels_evaluate_their_step_tables_at_compile_time():
 
 
 def test_no_kernel_of_the_library_holds_a_packed_fp32_instruction():
-    """Round 6 (DESIGN 5 "packed fp32", tools/ubench/pk_beside_mfma.hip): v_pk_add_f32 / v_pk_mul_f32 with an op_sel that reads a
+    """Round 6 (DESIGN 5 "packed fp32", profiles/r06_pk_beside_mfma.txt): v_pk_add_f32 / v_pk_mul_f32 with an op_sel that reads a
     high half return wrong results in lanes 48-63 while another wave of the SIMD alternates MFMAs with op_sel'd v_fma_mix_f32 -- the
     split-fp16 kernels' instruction mix.  The compiler wrote such instructions into esr_expgrad_fwd by itself (SLP vectoriser); the
     library is built with the packed-fp32 target feature off (esr_nerf_amd/build.py: NO_PACKED_FP32) and every source is checked."""

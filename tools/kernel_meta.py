@@ -1,35 +1,15 @@
-"""Registers, scratch, LDS and spills per kernel from `hipcc -S` of csrc/*.hip (or the files named on the command line):
+"""Registers, scratch, LDS and spills per kernel from the device assembly of csrc/*.hip (or the files named on the command
+line), compiled as the product compiles them (esr_nerf_amd/build.py: device_asm):
    python tools/kernel_meta.py [mlp_bf16.hip ...]      (CPU only; tests/test_isa.py asserts on it)"""
 import glob, os, re, subprocess, sys
-ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
-FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fvisibility=hidden", "-fno-fast-math",
-         "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops",        # = build.py: NO_PACKED_FP32
-         "-I" + os.path.join(ROOT, "include"), "-S", "--cuda-device-only"]
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from esr_nerf_amd.build import device_asm      # noqa: E402
 
 
-def _build_extra():
-    """The per-source flags of the product build (esr_nerf_amd/build.py: EXTRA), read from that file so the two cannot drift."""
-    src = open(os.path.join(ROOT, "esr_nerf_amd", "build.py")).read()
-    m = re.search(r"^EXTRA\s*=\s*(\{.*?\})\s*$", src, re.M | re.S)
-    import ast
-    return {k: tuple(v) for k, v in ast.literal_eval(m.group(1)).items()} if m else {}
-
-
-EXTRA = _build_extra()     # per-source flags, as esr_nerf_amd/build.py
-
-
-def asm_of(src, out=None, extra=()):
-    extra = tuple(extra) + EXTRA.get(os.path.basename(src), ())
-    if out is None:           # beside the library's objects: per checkout, never a file another user of the machine owns
-        out = os.path.join(ROOT, "esr_nerf_amd", "_obj", "asm_" + os.path.basename(src) + ".s")
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-    stamp = out + ".stamp"
-    deps = [src] + glob.glob(os.path.join(os.path.dirname(src), "*.h")) + [os.path.join(ROOT, "include", "esr_hip.h")]
-    key = str([(d, os.path.getmtime(d)) for d in deps]) + str(extra) + str(FLAGS)
-    if not (os.path.exists(out) and os.path.exists(stamp) and open(stamp).read() == key):
-        subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *extra, "-o", out, src], check=True, stderr=subprocess.DEVNULL)
-        open(stamp, "w").write(key)
-    return out
+def asm_of(src):
+    """Device assembly of the product source at path `src` (esr_nerf_amd/_obj/*.s, rebuilt when a source or a flag changes)."""
+    return device_asm(os.path.basename(src))
 
 
 def kernel_meta(asm_path):

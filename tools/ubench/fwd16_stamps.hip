@@ -19,6 +19,7 @@ __device__ unsigned long long g_stamps[256 * 8 * NS];     // [workgroup][trip][s
     } while (0)
 #include "../../esr_nerf_amd/csrc/mlp_bf16.hip"
 #include "../../esr_nerf_amd/csrc/mlp.hip"
+#include "../../esr_nerf_amd/csrc/mlp_split.hip"     // (esr_split_range_flag_ptr, which mlp.hip's host code names)
 
 int main()
 {
