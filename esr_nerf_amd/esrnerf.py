@@ -106,11 +106,12 @@ class _LtsRender(torch.autograd.Function):
         env = dict(mus=mus.detach(), lambdas=lambdas.detach(), lobes=lobes.detach())
         cfg = dict(num_2ndrays=model.num_2ndrays, num_ltspts=model.num_ltspts, normal_eps=batch["normal_eps"],
                    emit_eps=batch["emit_eps"], pdra=model.pdra_mode)
-        lctx, out = eng.lts_forward(scene, scene2, batch, grids, env, cfg, draws)
-        if eng.range_hit():       # a split-fp16 kernel's range flag: again on the f32 MFMA kernels, same draws (fine_engine.py)
-            with eng.f32_only():
-                pack()
-                lctx, out = eng.lts_forward(scene, scene2, batch, grids, env, cfg, eng.last_draws)
+        run = lambda d: eng.lts_forward(scene, scene2, batch, grids, env, cfg, d)
+
+        def rerun():              # a split-fp16 kernel's range flag: again on the f32 MFMA kernels, same draws (fine_engine.py)
+            pack()
+            return run(eng.last_draws)
+        lctx, out = eng.healed(lambda: run(draws), rerun)
         ctx.lctx, ctx.model = lctx, model
         ctx.set_materialize_grads(False)         # unused result tensors arrive as None and cost nothing
         ctx.shapes = [tuple(p.shape) for p in mlp_params]
@@ -155,13 +156,12 @@ class _FinetuneRender(torch.autograd.Function):
                      emit=model.emit_color.device_view(),
                      mask=model.mask_cache.density.view(*model.mask_cache.density.shape[2:]))
         cfg = dict(num_2ndrays=model.num_2ndrays, num_ltspts=model.num_ltspts)
-        fctx, out = eng.finetune_forward(model.scene_struct(), model.scene_struct(near=model.lts_near), batch, grids,
-                                         cfg, draws)
-        if eng.range_hit():       # (the range fallback, as in _LtsRender)
-            with eng.f32_only():
-                pack()
-                fctx, out = eng.finetune_forward(model.scene_struct(), model.scene_struct(near=model.lts_near), batch, grids,
-                                                 cfg, eng.last_draws)
+        run = lambda d: eng.finetune_forward(model.scene_struct(), model.scene_struct(near=model.lts_near), batch, grids, cfg, d)
+
+        def rerun():              # (the range fallback, as in _LtsRender)
+            pack()
+            return run(eng.last_draws)
+        fctx, out = eng.healed(lambda: run(draws), rerun)
         ctx.fctx, ctx.model = fctx, model
         ctx.shapes = [tuple(p.shape) for p in emo_params]
         ctx.set_materialize_grads(False)

@@ -15,6 +15,7 @@ boolean-mask compaction).
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 import os
 from dataclasses import dataclass
@@ -110,14 +111,23 @@ class _F32Only:
         self.eng = eng
 
     def __enter__(self):
-        e = self.eng
-        self.keep = (e.split_fwd, e.split_bwd, e.split_wgrad, e.split_tone_wgrad)
-        e.split_fwd = e.split_bwd = e.split_wgrad = e.split_tone_wgrad = False
+        self.keep, self.eng.split_fwd = self.eng.split_fwd, False
 
     def __exit__(self, *exc):
-        e = self.eng
-        e.split_fwd, e.split_bwd, e.split_wgrad, e.split_tone_wgrad = self.keep
+        self.eng.split_fwd = self.keep
         return False
+
+
+def _follows_forward(backward):
+    """Decorator of an engine's backward: when its forward ran on the f32 MFMA kernels (the range fallback: ``ctx.f32_only``),
+    so does the backward."""
+    @functools.wraps(backward)
+    def run(self, ctx, *args, **kw):
+        if ctx.f32_only and self.split_fwd:
+            with self.f32_only():
+                return backward(self, ctx, *args, **kw)
+        return backward(self, ctx, *args, **kw)
+    return run
 
 
 class _PackGroup:
@@ -174,16 +184,13 @@ class FineEngine:
         # the f32 MFMA kernels instead (A/B timing).  The planes' first halves are fp16: an input, a hidden activation or a
         # weight (x 64) beyond fp16's range cannot be carried.  Every split launch of a FORWARD raises a sticky device flag then
         # (the backward cannot overflow by construction: csrc/mlp.hip: split_gain_kernel), and the step that set it is RE-RUN
-        # on the f32 MFMA kernels before anything leaves it (`range_probe` / `range_hit` / `f32_only`; trainer.py,
-        # voxurff.py); ESR_SPLIT_STRICT=1 raises instead.
+        # on the f32 MFMA kernels before anything leaves it (`range_probe` / `range_hit` / `healed`; trainer.py,
+        # voxurff.py); ESR_SPLIT_STRICT=1 raises instead.  This one switch selects every split launch: `f32_only` and the
+        # streak cut-off turn it off.
         self.split_fwd = (not self.bf16) and os.environ.get("ESR_SPLIT_FWD", "1") != "0"
-        self.split_bwd = self.split_wgrad = self.split_tone_wgrad = self.split_fwd
         self.split_strict = os.environ.get("ESR_SPLIT_STRICT", "0") == "1"
         self.split_fallback_steps = 0     # steps (or image chunks) that were re-run on the f32 MFMA kernels
         self.packed_split: Dict[str, torch.Tensor] = {}
-        # net kinds on the split kernels: radiance (0), tone mapper (1), BRDF (2), emission (3)
-        self.split_kinds = {0, 1, 2, 3}
-        self.split_kinds_bwd = set(self.split_kinds)
         self._psplit = {}
         self.range_flag = None
         self._range_host = None
@@ -206,9 +213,23 @@ class FineEngine:
     # A ray that exceeds scene.max_steps (the march kernel's LDS bound) is skipped by the kernels and reported in the
     # plan header.  Single process: raise at once.  Data parallel (``defer_overflow``, set by the trainer steps): raising
     # on one rank would leave the others waiting in the gradient exchange, so the flag is remembered, summed over the
-    # ranks with the loss, and every rank raises together (trainer._check_overflow).
+    # ranks with the loss, and every rank raises together (trainer._Step._check_overflow).
     defer_overflow = False
     overflow_seen = False
+    range_strict_seen = False         # ESR_SPLIT_STRICT=1 under data parallelism: a range hit rode on the overflow word
+    _range_streak = 0                 # consecutive forwards that raised the range flag (RANGE_STREAK_MAX)
+
+    # net kinds on the split kernels: radiance (0), tone mapper (1), BRDF (2), emission (3); not the coarse renderer's (4)
+    split_kinds = split_kinds_bwd = frozenset({0, 1, 2, 3})
+    last_draws = None                 # the random draws of the last forward that drew any (lts_engine; the fallback replays them)
+
+    def _split_phase(self, on):
+        if bool(on) != self.split_fwd:
+            raise AttributeError("every split-fp16 launch follows split_fwd: set split_fwd instead")
+
+    # the per-phase switches of earlier versions (bench.py reads them): every phase follows split_fwd.  A write is accepted
+    # only when it agrees with split_fwd, so code that switches all four together keeps working.
+    split_bwd = split_wgrad = split_tone_wgrad = property(lambda self: self.split_fwd, _split_phase)
 
     def _overflow(self):
         if not self.defer_overflow:
@@ -232,7 +253,8 @@ class FineEngine:
     def range_hit(self) -> bool:
         """Wait for the probe (the host normally arrives here long after the device has passed it: trainer.py calls this
         with the input-gradient chain and the grid scatters queued behind the forward) and tell whether a split launch of
-        this step raised the flag.  The flag is cleared; the caller re-runs the step inside ``with eng.f32_only():``."""
+        this step raised the flag.  The flag is cleared; the caller re-runs the step inside ``with eng.f32_only():``
+        (``healed``, trainer._Step._step)."""
         ev, self._range_event = self._range_event, None
         if ev is None:
             return False
@@ -245,7 +267,7 @@ class FineEngine:
             if self.defer_overflow:
                 # data parallel: raising here would leave the other ranks waiting in the gradient exchange.  The hit travels
                 # with the march-overflow word (summed over the ranks with the loss) and EVERY rank raises at its next check
-                # (trainer._check_overflow / step.close()); this step's gradients must not be used.
+                # (trainer._Step._check_overflow / step.close()); this step's gradients must not be used.
                 self.overflow_seen = True
                 self.range_strict_seen = True
                 return False
@@ -255,12 +277,12 @@ class FineEngine:
             warnings.warn(self._RANGE_MSG + ": the step is re-run on the f32 MFMA kernels (slower; counted in "
                           "engine.split_fallback_steps)", RuntimeWarning, stacklevel=3)
         self.split_fallback_steps += 1
-        self._range_streak = getattr(self, "_range_streak", 0) + 1
+        self._range_streak += 1
         if self._range_streak >= self.RANGE_STREAK_MAX and self.split_fwd:
             # the cause persists (a weight beyond 1023, a gain bound beyond 2^18): every further step would run the split attempt,
             # wait on the host and then run again on the f32 MFMA kernels -- more than twice the work.  From here on the engine
             # IS the f32-MFMA engine (what ESR_SPLIT_FWD=0 selects), and says so once.
-            self.split_fwd = self.split_bwd = self.split_wgrad = self.split_tone_wgrad = False
+            self.split_fwd = False
             warnings.warn(f"{self.RANGE_STREAK_MAX} consecutive steps left fp16's range: this engine now runs every MLP launch on the "
                           "f32 MFMA kernels (as with ESR_SPLIT_FWD=0)", RuntimeWarning, stacklevel=3)
         return True
@@ -270,6 +292,17 @@ class FineEngine:
     def f32_only(self):
         """Context manager: every MLP launch inside runs on the f32 MFMA kernels (no range limit), on the same buffers."""
         return _F32Only(self)
+
+    def healed(self, run, rerun=None):
+        """``run()`` with the split kernels' range fallback: when the probe at the end of its forward says a split launch
+        raised the flag, ``rerun`` (default: ``run``) runs again on the f32 MFMA kernels and its result is returned.  A probe
+        that an earlier forward left unexamined is dropped first (a forward may end before its own probe)."""
+        self._range_event = None
+        out = run()
+        if self.range_hit():
+            with self.f32_only():
+                out = (rerun or run)()
+        return out
 
     def _run(self, name, fn, *args):
         """Enqueue one C-ABI call; with timing on, bracket it with HIP events recorded on the
@@ -403,7 +436,7 @@ class FineEngine:
 
     def mlp_dgrad(self, kind, packed, *rest):
         if not self.bf16:
-            planes = self._psplit.get(packed.value) if (self.split_fwd and self.split_bwd and kind in self.split_kinds_bwd) else None
+            planes = self._psplit.get(packed.value) if self.split_fwd else None
             if planes is not None:                      # (..., dX, stream) -> (..., dX, amax = NULL, stream)
                 return self.L.esr_mlp_dgrad_split(kind, planes, *rest[:-1], None, rest[-1])
             return self.L.esr_mlp_dgrad(kind, packed, *rest)
@@ -435,11 +468,8 @@ class FineEngine:
         code): wait for the forward's range probe and, when a split launch raised the flag, run the forward again on the f32
         MFMA kernels.  ``heal=False`` (trainer.FineStep): the caller examines the probe itself (``range_hit``) where the wait
         is free -- with the backward's input-gradient chain queued -- and re-runs its whole step."""
-        out = self._forward(scene, rays_o, rays_d, viewdirs, em_modes, mask_density, sdf, off_color, emo_color, prelude)
-        if heal and self.range_hit():
-            with self.f32_only():
-                out = self._forward(scene, rays_o, rays_d, viewdirs, em_modes, mask_density, sdf, off_color, emo_color, prelude)
-        return out
+        run = lambda: self._forward(scene, rays_o, rays_d, viewdirs, em_modes, mask_density, sdf, off_color, emo_color, prelude)
+        return self.healed(run) if heal else run()
 
     def _forward(self, scene, rays_o, rays_d, viewdirs, em_modes, mask_density, sdf, off_color, emo_color, prelude=None):
         """-> (ctx, alphainv_last [N], srgb_marched [N,3], lin_marched [N,3]).
@@ -506,7 +536,6 @@ class FineEngine:
         tiles_all = tiles_on + (n_off + 31) // 32
         if overflow & 1:                                            # (bit 1: the split kernels' range flag, informational)
             self._overflow()
-        self._range_event = None
         ctx = FineCtx(scene=scene, n_rays=n, tiles_on=tiles_on, tiles_all=tiles_all,
                       counts=dict(m0=m0, m1=m1, m2=m2, m3=n_on + n_off, n_on=n_on, n_off=n_off),
                       rays_o=rays_o, rays_d=rays_d, viewdirs=viewdirs, off3=rb["off3"], mask_density=mask_density, sdf=sdf,
@@ -571,11 +600,7 @@ class FineEngine:
     @torch.no_grad()
     def evaluate(self, *args):
         """``_evaluate`` + the split kernels' range fallback (one more run on the f32 MFMA kernels when the flag was raised)."""
-        out = self._evaluate(*args)
-        if self.range_hit():
-            with self.f32_only():
-                out = self._evaluate(*args)
-        return out
+        return self.healed(lambda: self._evaluate(*args))
 
     def _evaluate(self, scene, rays_o, rays_d, viewdirs, mask_density, sdf, off_color, emo_color, pos_rt, far,
                   em_mode: int):
@@ -595,7 +620,6 @@ class FineEngine:
         self.plan_host.copy_(self.plan_dev, non_blocking=True)
         torch.cuda.current_stream(dev).synchronize()
         _, _, _, T, m0, m1, m2, overflow = [int(v) for v in self.plan_host.tolist()]
-        self._range_event = None
         if overflow & 1:
             raise RuntimeError("a ray exceeded scene.max_steps; the LDS bound of the march kernel is wrong")
         z3 = lambda: torch.zeros(n, 3, dtype=torch.float32, device=dev)
@@ -642,6 +666,7 @@ class FineEngine:
         return out
 
     # -- backward ----------------------------------------------------------------
+    @_follows_forward
     def backward(self, ctx: FineCtx, g_last, g_srgb, g_lin, grads: Dict[str, Optional[torch.Tensor]],
                  after_grids=None):
         """Accumulates into the (zero-initialised, reference-layout) tensors of ``grads``:
@@ -654,12 +679,6 @@ class FineEngine:
         ``after_grids()`` is called once the grid gradients are complete in stream order: the
         data-parallel step starts the (large) grid all-reduce there, underneath the wgrad kernels.
         A forward that ran on the f32 MFMA kernels (the range fallback) gets an f32 backward."""
-        if ctx.f32_only and self.split_fwd:
-            with self.f32_only():
-                return self._backward(ctx, g_last, g_srgb, g_lin, grads, after_grids)
-        return self._backward(ctx, g_last, g_srgb, g_lin, grads, after_grids)
-
-    def _backward(self, ctx: FineCtx, g_last, g_srgb, g_lin, grads, after_grids=None):
         L, ws = self.L, self.ws
         sp = C.byref(ctx.scene)
         to, ta = ctx.tiles_on, ctx.tiles_all
@@ -673,7 +692,7 @@ class FineEngine:
         # (a third stream for the scatters was measured slower on MI355X -- C2: 4.08 ms without, 4.19-4.47 ms with: the
         #  atomics-heavy scatters slow the matrix kernels more than they hide -- and is gone)
         overlap = self.overlap_wgrad and ta > 0
-        split = not self.bf16 and self.split_fwd and self.split_bwd
+        split = not self.bf16 and self.split_fwd
 
         # the march backward's value-tap gradients of the recorded samples ride on the feature backward's SDF window
         # (ws["dsdf"]) instead of 8 L2 atomics each; not with neus_alpha "grad" (its gradient taps scatter anyway)
@@ -708,7 +727,7 @@ class FineEngine:
         def tone_wgrad(s_):
             # from Xt and dzt alone: the hidden layer is recomputed inside (tone_wgrad.hip)
             (w0, w1), (b0, _) = self._raw["tone"]
-            if split and self.split_tone_wgrad:
+            if split:
                 # products on the 16-bit matrix cores; the gradient operand's scale: ctx.amax_t, left behind by the split
                 # input-gradient kernel (max |dzt| x the net's gain bound: no overflow by construction)
                 self._run("tone_wgrad", L.esr_tone_wgrad_recompute_split, _lib.ptr(ws["Xt"]), _lib.ptr(ws["dzt"]), _lib.ptr(w0.detach()),
@@ -741,7 +760,7 @@ class FineEngine:
                 jb.gw, jb.gb = C.addressof(gwa), C.addressof(gba)
                 if ctx.x16:
                     jb.X16 = ws["X16"].data_ptr()
-                if split and self.split_wgrad:          # (non-NULL amax selects the split-fp16 weight-gradient kernel)
+                if split:                               # (non-NULL amax selects the split-fp16 weight-gradient kernel)
                     jb.amax = ctx.amax.data_ptr()
             self._run("mlp_wgrad(all)", L.esr_mlp_wgrad_batch, jobs, len(todo), 1 if self.bf16 else 0,
                       _lib.ptr(self.wgrad_scratch), C.c_int64(self.wgrad_scratch.numel()), s_)

@@ -321,7 +321,7 @@ class ShardedGrids:
         ``grad_shard``; asynchronous on RCCL."""
         if flat_grad.numel() != self.padded:
             # (the trainer steps lay their flat buffer out with the grid part padded to ``self.padded`` once
-            # ``step.sharded`` is attached -- trainer._grid_pad -- so this 218 MB-per-step copy is the fallback for other callers)
+            # ``step.sharded`` is attached -- trainer._Step._alloc_grads -- so this 218 MB-per-step copy is the fallback for other callers)
             if not hasattr(self, "_gpad") or self._gpad.device != flat_grad.device:
                 self._gpad = torch.zeros(self.padded, dtype=torch.float32, device=flat_grad.device)
             self._gpad[: self.n].copy_(flat_grad[: self.n])

@@ -18,13 +18,14 @@ from __future__ import annotations
 import ctypes as C
 import math
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import Dict, List, Optional
 
 import numpy as np
 import torch
 
 from . import _lib
-from .fine_engine import DX_ROWS, KIND_RADIANCE, KIND_TONEMAP, X_ROWS, XT_ROWS, FineEngine
+from .fine_engine import DX_ROWS, KIND_RADIANCE, KIND_TONEMAP, X_ROWS, XT_ROWS, FineEngine, _follows_forward
 
 KIND_BRDF, KIND_EMIT = 2, 3
 ACT_SOFTPLUS, ACT_SIGMOID = 0, 1
@@ -228,7 +229,6 @@ class LtsEngine(FineEngine):
         # on one box: none 3.29 ms, {1} 3.18; C4 lts f32: 3.99 -> 3.84.  {1,2}: inside the noise of {1}.
         self.eps_stream = True              # (lts_forward: the perturbed heads' pass on a stream of its own)
         self.scatter_streamed = {1}
-        self.last_draws = None              # the random draws of the last lts_forward (the range fallback replays them)
         for k, kind in (("brdf", KIND_BRDF), ("emit", KIND_EMIT)):
             self.packed[k] = torch.empty(self.L.esr_mlp_packed_floats(kind), dtype=torch.float32,
                                          device=self.device)
@@ -439,11 +439,11 @@ class LtsEngine(FineEngine):
             s = self._s()
             recompute = kind == KIND_TONEMAP
             amax = None
-            if kind in self.split_kinds_bwd and self.split_fwd and self.split_bwd and net in self.packed_split:
+            if self.split_fwd and net in self.packed_split:
                 # (radiance, BRDF, emission nets.)  max |dz| of this net and pass, left behind by the input-gradient kernel:
                 # the scale of the split-fp16 weight-gradient job (esr_wgrad_job_t::amax)
-                amax = self._z(1) if (self.split_wgrad and self._wgrad_jobs is not None) else None
-                if recompute and self.split_tone_wgrad:
+                amax = self._z(1) if self._wgrad_jobs is not None else None
+                if recompute:
                     amax = self._z(1)                      # max |dzt|: the scale of the tone mapper's split weight gradients
                 self._run(f"mlp_dgrad({net})[{P.name}]", self.L.esr_mlp_dgrad_split, kind, _lib.ptr(self.packed_split[net]),
                           _lib.ptr(dz), t0, t1, _lib.ptr_array(M), _lib.ptr_array([None] * nh if recompute else dZ), _lib.ptr(dX),
@@ -455,7 +455,7 @@ class LtsEngine(FineEngine):
                 (w0, w1), (b0, _) = self._raw[net]
 
                 def tone_wgrad(amax_t=amax):
-                    if self.split_tone_wgrad and amax_t is not None:       # (the scale source comes from the split input-gradient kernel)
+                    if amax_t is not None:       # (the scale source comes from the split input-gradient kernel)
                         self._run(f"tone_wgrad[{P.name}]", self.L.esr_tone_wgrad_recompute_split, _lib.ptr(x), _lib.ptr(dz),
                                   _lib.ptr(w0.detach()), _lib.ptr(b0.detach()), _lib.ptr(w1.detach()), _lib.ptr(amax_t), t0, t1,
                                   _lib.ptr(gw[0]), _lib.ptr(gb[0]), _lib.ptr(gw[1]), _lib.ptr(gb[1]), _lib.ptr(self.tone_scratch),
@@ -587,11 +587,7 @@ class LtsEngine(FineEngine):
         """``_evaluate_lts`` + the split kernels' range fallback: one more run on the f32 MFMA kernels, with the same
         scattering draws, when a split launch raised the flag."""
         args = (scene, scene2, rays_o, rays_d, viewdirs, grids, envmap, pos_rt, far, em_mode, render_pbr, chunk_sz, num_2ndrays)
-        out = self._evaluate_lts(*args, draws)
-        if self.range_hit():
-            with self.f32_only():
-                out = self._evaluate_lts(*args, self._eval_draws)
-        return out
+        return self.healed(lambda: self._evaluate_lts(*args, draws), lambda: self._evaluate_lts(*args, self._eval_draws))
 
     def _evaluate_lts(self, scene, scene2, rays_o, rays_d, viewdirs, grids, envmap, pos_rt, far, em_mode, render_pbr, chunk_sz,
                       num_2ndrays, draws=None):
@@ -605,7 +601,6 @@ class LtsEngine(FineEngine):
         n = rays_o.shape[0]
         P0 = self.prim
         self._eval_draws = []                     # the chunks' scattering draws (replayed by the range fallback)
-        self._range_event = None
         cnt3, off3, last = self._march(P0, scene, rays_o, rays_d, torch.zeros(n, dtype=torch.int64, device=dev),
                                        grids["mask"], sdf, viewdirs=viewdirs)
         T, m3 = P0.tiles_all, P0.counts["m3"]
@@ -731,11 +726,7 @@ class LtsEngine(FineEngine):
     # ------------------------------------------------------------------ PDRA regrouping queries
     @torch.no_grad()
     def eval_query(self, *args):
-        out = self._eval_query(*args)
-        if self.range_hit():
-            with self.f32_only():
-                out = self._eval_query(*args)
-        return out
+        return self.healed(lambda: self._eval_query(*args))
 
     def _eval_query(self, scene, rays_o, rays_d, viewdirs, mask_density, sdf, emit_grid, what: str):
         """``ESRNeRF.eval_emit`` (what="emit", esrnerf.py:1299-1358: composited emission) or ``eval_esp``
@@ -743,7 +734,6 @@ class LtsEngine(FineEngine):
         L, s, dev = self.L, self._s(), self.device
         n = rays_o.shape[0]
         P0 = self.prim
-        self._range_event = None
         self._march(P0, scene, rays_o, rays_d, torch.zeros(n, dtype=torch.int64, device=dev), mask_density, sdf,
                     viewdirs=viewdirs)
         T = P0.tiles_all
@@ -787,7 +777,6 @@ class LtsEngine(FineEngine):
         ``num_2ndrays`` secondary rays.  grids: sdf, emo, brdf, emit (the frozen copy feeding the emission head),
         mask.  Only the emo colour grid and the emo net receive gradients (finetune_backward)."""
         L, s, dev = self.L, self._s(), self.device
-        self._range_event = None
         sdf, emog, brdfg, emitg = grids["sdf"], grids["emo"], grids["brdf"], grids["emit"]
         rays_o, rays_d, viewdirs = batch["rays_o"], batch["rays_d"], batch["viewdirs"]
         N = rays_o.shape[0]
@@ -865,24 +854,23 @@ class LtsEngine(FineEngine):
         off_hat = torch.empty(2 * Pn, 3, device=dev)          # the off half of the combine is unused here
         emo_hat = torch.empty(2 * Pn, 3, device=dev)
         self._run("lts_combine_fwd", L.esr_lts_combine_fwd, C.byref(a), _lib.ptr(off_hat), _lib.ptr(emo_hat), s)
-        ctx = dict(scene=scene, n_pts=Pn, held=held, keep=(pts2, vd2, sdf2, last2), f32_only=not self.bf16 and not self.split_fwd)
+        ctx = SimpleNamespace(scene=scene, n_pts=Pn, held=held, keep=(pts2, vd2, sdf2, last2),
+                              f32_only=not self.bf16 and not self.split_fwd)
         self.last_draws = dict(idx=idx_ref, dirs=raw)
         self.range_probe()
         return ctx, {"lin/pbr/emo": emo_pt, "lin/pbr/emo_hat": emo_hat}
 
+    @_follows_forward
     def finetune_backward(self, ctx, g_emo, grads):
         """g_emo [2*P,3] -> grads["emo"] (colour grid, channels-last), grads["emo_w"], grads["emo_b"]."""
-        if ctx.get("f32_only") and self.split_fwd:
-            with self.f32_only():
-                return self.finetune_backward(ctx, g_emo, grads)
         P1, dev = self.pts, self.device
-        T1, Pn = P1.tiles_all, ctx["n_pts"]
+        T1, Pn = P1.tiles_all, ctx.n_pts
         ga = torch.zeros(T1 * 32, 3, device=dev)
         ga[: 2 * Pn] = g_emo
         gt = P1.from_rowmajor("emo.ga", 4, ga)
         dz = self._act(P1, "emo.z", "emo.dz", 4, 3, ACT_SOFTPLUS, bwd_g=gt)
         dX = self._net_bwd(P1, "emo", KIND_RADIANCE, 88, 0, T1, dz, grads["emo_w"], grads["emo_b"])
-        self._feat_bwd(P1, ctx["scene"], [(dX, None, grads["emo"], 0, T1)], None)
+        self._feat_bwd(P1, ctx.scene, [(dX, None, grads["emo"], 0, T1)], None)
 
     # ------------------------------------------------------------------ forward
     def lts_forward(self, scene, scene2, batch, grids, envmap, cfg, draws=None, prelude=None):
@@ -894,7 +882,6 @@ class LtsEngine(FineEngine):
         absent they are drawn exactly where the reference draws them."""
         L, s, dev = self.L, self._s(), self.device
         sdf, offg, emog, brdfg = grids["sdf"], grids["off"], grids["emo"], grids["brdf"]
-        self._range_event = None
         self._zero_arena_begin()
         rays_o, rays_d, viewdirs = batch["rays_o"], batch["rays_d"], batch["viewdirs"]
         N = rays_o.shape[0]
@@ -1109,15 +1096,13 @@ class LtsEngine(FineEngine):
         return ctx, out
 
     # ------------------------------------------------------------------ backward
+    @_follows_forward
     def lts_backward(self, ctx: LtsCtx, g: Dict[str, Optional[torch.Tensor]], grads, after_grids=None):
         """g: gradients w.r.t. the tensors of lts_forward's dict (None = zero).  grads: zero-initialised
         dict: sdf, off, emo, brdf grids; {off,emo,tone,brdf,emit}_{w,b} lists; mus, lambdas, lobes.
         Order on the main stream: every input-gradient chain and grid scatter, then ``after_grids()`` (the
         data-parallel step exchanges the dense-grid gradients there); the weight-gradient launches run beside it on
         a second stream (or, without ``overlap_wgrad``, after it) and are joined at the end."""
-        if ctx.f32_only and self.split_fwd:         # (the range fallback's forward: fine_engine.FineEngine.backward)
-            with self.f32_only():
-                return self.lts_backward(ctx, g, grads, after_grids)
         main = torch.cuda.current_stream(self.device)
         self._wgrad_jobs, self._wgrad_extra = [], []
         self._wgrad_flushed = False

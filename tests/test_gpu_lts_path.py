@@ -559,7 +559,7 @@ def test_lts_step_heals_a_range_overflow_in_the_same_step_with_the_same_draws(st
     step.close()
     m2, step2 = build()
     e2 = m2.engine
-    e2.split_fwd = e2.split_bwd = e2.split_wgrad = e2.split_tone_wgrad = False
+    e2.split_fwd = False
     step2.forward_loss_backward(b, s_val)
     poke(m2)
     loss2, G2, _ = step2.forward_loss_backward(b, s_val, draws=draws)

@@ -680,7 +680,7 @@ def _heal_case(make_bad, steps_before=1):
         m = build_gpu_model(sc, seed=1, grid_seed=2)
         eng = m.engine
         if mode == "f32":
-            eng.split_fwd = eng.split_bwd = eng.split_wgrad = eng.split_tone_wgrad = False
+            eng.split_fwd = False
         else:
             assert eng.split_fwd
             eng.range_flag.zero_()
@@ -793,7 +793,7 @@ def test_a_persistent_cause_switches_the_engine_to_the_f32_kernels_and_strict_mo
     m2.emo_rgbnet.layers()[0].bias.data[3] = 7.0e4
     FineStep(m2).forward_loss_backward(b, 60.0)                            # no exception on this rank ...
     torch.cuda.synchronize()
-    assert e2.overflow_seen and getattr(e2, "range_strict_seen", False)     # ... the hit rides on the overflow word
+    assert e2.overflow_seen and e2.range_strict_seen     # ... the hit rides on the overflow word
 
 
 def test_autograd_route_heals_in_the_forward():
@@ -810,7 +810,7 @@ def test_autograd_route_heals_in_the_forward():
         m.train()
         eng = m.engine
         if mode == "f32":
-            eng.split_fwd = eng.split_bwd = eng.split_wgrad = eng.split_tone_wgrad = False
+            eng.split_fwd = False
         else:
             eng.range_flag.zero_()
         m.off_rgbnet.layers()[1].weight.data[5, 9] = -3000.0

@@ -432,20 +432,19 @@ def test_point_draw_on_the_library_worker_equals_numpy_choice():
     assert os.WEXITSTATUS(os.waitpid(pid, 0)[1]) == 0
 
 
-def test_deferred_march_overflow_raises_on_the_next_step():
+def test_step_raises_a_deferred_march_overflow_on_the_next_step():
     """Data-parallel steps do not raise inside the step when a ray exceeded the march bound (the other ranks would hang in
     the exchange): the flag is reduced with the loss and every rank raises at the start of its next step."""
-    import types
-    from esr_nerf_amd import trainer
-    step = types.SimpleNamespace()
-    trainer._check_overflow(step)                                   # nothing published yet: no-op
+    from esr_nerf_amd.trainer import FineStep
+    step = FineStep(model=None)                                     # (the overflow word needs no model and no GPU)
+    step._check_overflow()                                          # nothing published yet: no-op
     lf = torch.tensor([0.25, 0.0])
-    trainer._publish_overflow(step, lf)
-    trainer._check_overflow(step)                                   # flag 0: fine
-    trainer._publish_overflow(step, torch.tensor([0.25, 2.0]))      # two ranks saw an overflow
+    step._publish_overflow(lf)
+    step._check_overflow()                                          # flag 0: fine
+    step._publish_overflow(torch.tensor([0.25, 2.0]))               # two ranks saw an overflow
     with pytest.raises(RuntimeError, match="max_steps"):
-        trainer._check_overflow(step)
-    trainer._check_overflow(step)                                   # raised once, then cleared
+        step._check_overflow()
+    step._check_overflow()                                          # raised once, then cleared
 
 
 def test_render_utils_shim_has_every_name_of_the_two_pybind_modules():
