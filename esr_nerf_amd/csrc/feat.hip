@@ -670,7 +670,9 @@ __global__ void __launch_bounds__(256, 2) feat_bwd_kernel(FeatParams P)
 #pragma unroll
         for (int k = 0; k < MAX_SRC; ++k)
             if (k < P.n_src && t >= P.src_t0[k] && t < P.src_t1[k]) { if (!nact) k_one = k; ++nact; }
-        float r_n[3][4], r_dn[3][4], r_nrm[4], r_df[2][2][4], r_dsdf = 0.f, r_d3[3] = {0.f, 0.f, 0.f};
+        // r_dn / r_df start at zero: a tile inside [t_begin, t_end) that no source covers (the launch spans every tile
+        // when dsdf_extra, dsdf_out or grad4 is given) has no stencil gradient, only its dsdf_extra / grad4 terms
+        float r_n[3][4], r_dn[3][4] = {}, r_nrm[4], r_df[2][2][4] = {}, r_dsdf = 0.f, r_d3[3] = {0.f, 0.f, 0.f};
         auto dx_rows = [&](const float *dXt, bool first) {
             auto put = [&](float &dst, int row) { const float v = dXt[row * 32]; dst = first ? v : dst + v; };
 #pragma unroll
@@ -806,7 +808,8 @@ __global__ void __launch_bounds__(256, 2) feat_bwd_kernel(FeatParams P)
                 // on the next, 0 elsewhere -- three instructions per cell instead of two compares, two selects and two adds
                 const float baseA = (float)(iA - 2);
                 auto deposit = [&](float ixA, float d) {
-                    const float t = ixA - baseA;                     // exact: small integers and an index < 2^12
+                    // exact for iA >= 2; for iA < 2, t can have a larger exponent than ixA and is rounded once (<= 2^-22)
+                    const float t = ixA - baseA;
 #pragma unroll
                     for (int o = 0; o < 6; ++o) acc6[o] = fmaf(fmaxf(1.f - fabsf(t - (float)o), 0.f), d, acc6[o]);
                 };
