@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libesr_hip.so")
 # developer experiments only (python -m esr_nerf_amd.build --variant builds alternative libraries; tools/ab_env.sh times them
 # side by side on one box)
 LIB_PATH = os.environ.get("ESR_LIB_PATH", LIB_PATH)
-ABI_VERSION = 26
+ABI_VERSION = 27
 _lib = None
 
 
@@ -121,6 +121,7 @@ EXPORTS = [
     "esr_mlp_packed_bf16_elems", "esr_mlp_pack_bf16", "esr_mlp_fwd_bf16", "esr_mlp_dgrad_bf16", "esr_mlp_wgrad_bf16",
     "esr_brick_floats", "esr_brick_flags", "esr_brick_pack", "esr_brick_unpack", "esr_brick_list", "esr_brick_list_scratch_ints",
     "esr_smooth_grad_tv_fwd", "esr_smooth_grad_tv_bwd", "esr_host_choice_noreplace", "esr_host_choice_start", "esr_host_choice_wait",
+    "esr_mesh_field", "esr_mesh_blocks", "esr_mesh_count", "esr_mesh_emit",
 ]
 
 
@@ -150,6 +151,8 @@ def lib() -> C.CDLL:
             L.esr_mlp_packed_split_elems.restype = C.c_int64
         if hasattr(L, "esr_mlp_split_gain_offset"):
             L.esr_mlp_split_gain_offset.restype = C.c_int64
+        if hasattr(L, "esr_mesh_blocks"):
+            L.esr_mesh_blocks.restype = C.c_int64
         if L.esr_abi_version() != ABI_VERSION:
             raise RuntimeError("libesr_hip.so ABI version mismatch: rebuild")
         _lib = L

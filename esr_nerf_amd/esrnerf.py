@@ -9,7 +9,8 @@ node over the kernels of libesr_hip.so (esr_nerf_amd/lts_engine.py).
 
 ``forward_finetune`` (re-lighting fine-tune target, esrnerf.py:241-484) runs on the same kernels.
 ``eval_emit`` / ``eval_esp`` (the PDRA trainer's regrouping queries) are forward-only passes over the same kernels.
-``forward_evaluate`` renders images incl. the per-sample light-transport decomposition.  ``render_envmap`` / ``extract_geometry`` are torch utilities outside the path.
+``forward_evaluate`` renders images incl. the per-sample light-transport decomposition.  ``render_envmap`` is a torch utility outside the path;
+``extract_geometry`` (via VoxurfF) runs the HIP field and marching cubes of esr_nerf_amd/mesh.py on a GPU-resident model.
 """
 from __future__ import annotations
 

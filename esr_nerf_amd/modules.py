@@ -270,7 +270,13 @@ def extract_sdf_field(model, resolution=512, batch_size=64, smooth=True, sigma=0
 
 
 def extract_geometry(model, resolution=512, threshold=0.0, batch_size=64, smooth=True, sigma=0.5):
-    """(vertices, triangles) of the zero level set, as the reference's ``extract_geometry`` (needs PyMCubes)."""
+    """(vertices, triangles) of the ``threshold`` level set of -sdf, as the reference's ``extract_geometry``.
+
+    A model whose SDF grid is on the GPU runs the HIP field and marching cubes of ``esr_nerf_amd.mesh`` (``batch_size`` has
+    no effect there).  A CPU-resident model keeps the torch field and PyMCubes, as the reference (needs ``mcubes``)."""
+    if model.sdf.grid.is_cuda:
+        from .mesh import extract_geometry as extract_geometry_hip
+        return extract_geometry_hip(model, resolution, threshold, smooth, sigma)
     try:
         import mcubes
     except ImportError as e:                                         # not in this image; the reference requires it too

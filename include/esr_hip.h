@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 26
+#define ESR_ABI_VERSION 27
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -1007,6 +1007,34 @@ int esr_brick_unpack(const float *packed, const int64_t *brick_idx, int64_t n_id
 int64_t esr_brick_list_scratch_ints(void);
 int esr_brick_list(const uint8_t *flags, int64_t n_bricks, int64_t cap, int64_t *idx, int64_t *count, int32_t *scratch,
                    void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * G. Mesh export (extract_geometry): the -sdf lattice field and marching cubes
+ * ------------------------------------------------------------------------- */
+
+/*
+ * The field of extract_geometry -- replaces app/fine/model/voxurff.py:745-770 (-grid_sample of the SDF grid) over
+ * app/utils/base/functions.py:108-139 (extract_fields' lattice).  u[i,j,k] = -trilinear(sdf, (xs[i], ys[j], zs[k])) with
+ * F.grid_sample(align_corners=True)'s arithmetic.  sdf [gx,gy,gz] (raw, or smoothed by esr_gauss3d_fwd); box_host [host]
+ * xyz_min[3], xyz_max[3]; xs [r0], ys [r1], zs [r2] the lattice axes (torch.linspace); u [r0,r1,r2].  2 <= r <= 1024.
+ */
+int esr_mesh_field(const float *sdf, int32_t gx, int32_t gy, int32_t gz, const float *box_host, const float *xs,
+                   const float *ys, const float *zs, int32_t r0, int32_t r1, int32_t r2, float *u, void *stream);
+/*
+ * Marching cubes of u [r0,r1,r2] at `threshold` -- replaces mcubes.marching_cubes.  Count -> scan -> emit, no atomics:
+ *   esr_mesh_blocks:  nb, the number of node blocks (a negative ESR_E* for bad dims); the caller allocates
+ *                     counts / offsets as int64 [2, nb]
+ *   esr_mesh_count:   counts[0][b] = vertices, counts[1][b] = triangles of block b
+ *   esr_mesh_emit:    offsets = the exclusive scan of counts along b; vid int32 [r0*r1*r2] scratch (every vertex id must
+ *                     fit 31 bits); vertices f64 [V,3] in index space, triangles i64 [F,3] (V, F = the count totals).
+ * A node is inside iff u > threshold; one vertex per crossed lattice edge at n + t e_a, t = (thr - u[n]) / (u[n+e_a] - u[n])
+ * in f64; vertices ordered by owner node then axis, triangles by cell then case-table order (csrc/mc_table.h);
+ * (b - a) x (c - a) points towards decreasing u.
+ */
+int64_t esr_mesh_blocks(int32_t r0, int32_t r1, int32_t r2);
+int esr_mesh_count(const float *u, int32_t r0, int32_t r1, int32_t r2, float threshold, int64_t *counts, void *stream);
+int esr_mesh_emit(const float *u, int32_t r0, int32_t r1, int32_t r2, float threshold, const int64_t *offsets,
+                  int32_t *vid, double *vertices, int64_t *triangles, void *stream);
 
 #ifdef __cplusplus
 }
