@@ -13,10 +13,16 @@ the named path (reported separately, not here).  With N > 1 ever
 runs the same step on its own 4096 rays (weak scaling) and the gradients are
 all-reduced over RCCL inside the timed region.
 
-Prints ONE JSON line (rank 0).  Extra objects:
-  roofline      dominant kernel, algorithmic FLOPs / HIP-event time vs the f32 MFMA peak
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps, writes
+--dump-outputs if asked and prints the line.  --full adds everything else the benchmark
+measures, each outside the timed steps:
+  roofline      dominant kernel, algorithmic FLOPs / HIP-event time vs the f32 MFMA peak,
+                and the per-kernel breakdown of three instrumented steps behind the timed ones
+  optimizer_step, grad_zero_fill, tv_terms   the sections reported beside the step, timed alone
   cpu_baseline  oracle/fine_path.py (the CPU port of the reference path) timed on
                 the host cores on a bounded ray sample of the same scene (N=1 only)
+  other_workloads   the other BASELINE configs, one child process each (headline command only)
+  grad_exchange_phases_ms, grad_sync_sweep_ms   N > 1: the exchange's fixed costs and forms
 
 --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned
 (loss, every parameter gradient, and the LTS steps' forward outputs) as DIR/<name>.npy, float32
@@ -90,6 +96,10 @@ def parse():
                     help="C2 only: the production-size grid of the fine stage's end (cfg/app/fine.yaml:41-43), world "
                          "256 x 256 x 256, same 4096 rays x 128 surviving samples (synthetic.CONFIGS['C2g256']) -- a labelled "
                          "robustness line, NOT BASELINE's workload")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else (module docstring): roofline and kernel breakdown, "
+                         "optimizer / zero-fill / TV timings, CPU baseline, other workloads, exchange phases and sweep. The "
+                         "--no-* switches below leave single sections of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-rays", type=int, default=None,
                     help="rays of the CPU baseline sample (default: the whole batch in the fine stage -- SURVEY 8(d): same N, "
@@ -108,9 +118,10 @@ def parse():
     ap.add_argument("--sync-sweep", action="store_true",
                     help="N > 1: after the timed steps, time 10 more steps under each gradient-exchange form (sparse / dense; "
                          "shard is left out: it needs the sharded optimizer) and print grad_sync_sweep_ms, so that ONE multi-GPU "
-                         "record is enough to pick the default of trainer._grid_sync.  On by itself for N = 2..4 (outside the timed "
-                         "region, ~0.1 s); for N >= 5 only with this flag: there the non-default form is the one no real node has run yet")
-    ap.add_argument("--no-sync-sweep", action="store_true", help="N = 2..4: leave the sweep out")
+                         "record is enough to pick the default of trainer._grid_sync.  On by itself in a --full run for N = 2..4 "
+                         "(outside the timed region, ~0.1 s); otherwise only with this flag: for N >= 5 the non-default form is the "
+                         "one no real node has run yet")
+    ap.add_argument("--no-sync-sweep", action="store_true", help="--full, N = 2..4: leave the sweep out")
     ap.add_argument("--step-times", action="store_true",
                     help="diagnostic: record a HIP event behind every timed step and print the per-step times (ms) to stderr -- how "
                          "long the step takes to reach its steady state after the warm-up (clocks, caches)")
@@ -422,10 +433,10 @@ def other_workloads(budget_s=170.0):
     for name, args, env in OTHER_WORKLOADS:
         left = budget_s - (time.perf_counter() - t_start)
         if left < 20.0:
-            out[name] = {"skipped": "time budget of the default run spent"}
+            out[name] = {"skipped": "time budget of the --full run spent"}
             continue
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), *args, "--steps", "30", "--warmup", "10", "--no-cpu-baseline",
-               "--no-optimizer", "--no-other"]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), *args, "--steps", "30", "--warmup", "10", "--full",
+               "--no-cpu-baseline", "--no-optimizer", "--no-other"]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=left, cwd=ROOT, env=dict(os.environ, **env))
             line = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -633,13 +644,14 @@ def main():
     gc.collect()
     gc.freeze()
     gc.disable()
-    n_prof = 0 if a.no_kernel_timing else 3
+    n_prof = 3 if (a.full and not a.no_kernel_timing) else 0
     dump = a.dump_outputs is not None and rank == 0
     for i_ in range(a.warmup):
         one(i_)
     # timed region: exactly K steps; the fine stage's three large launches carry one event pair each (on their stream) -- which
-    # of them dominates is decided from the breakdown afterwards
-    in_region = ["mlp_fwd(rad)", "mlp_dgrad(rad)", "mlp_wgrad(all)"] if (n_prof and stage == "fine") else None
+    # of them dominates is decided from the breakdown afterwards.  The pairs are part of the timed steps in a plain run too
+    # (only --full reads them): a plain and a --full line time the same steps
+    in_region = ["mlp_fwd(rad)", "mlp_dgrad(rad)", "mlp_wgrad(all)"] if (not a.no_kernel_timing and stage == "fine") else None
     eng.enable_timing(in_region is not None, only=in_region)
     if pg is not None:
         import torch.distributed as dist
@@ -674,7 +686,7 @@ def main():
         os.makedirs(a.dump_outputs, exist_ok=True)
         for name_, arr_ in dumped.items():
             np.save(os.path.join(a.dump_outputs, name_ + ".npy"), arr_)
-    kern = eng.timing_summary() if in_region else {}     # the bracketed launches: name -> (launches, total ms)
+    kern = eng.timing_summary() if (in_region and a.full) else {}     # the bracketed launches: name -> (launches, total ms)
     eng.enable_timing(False)
     # the instrumented steps (outside W and K; every rank runs them: a step is collective when N > 1)
     breakdown, dominant, prof_counts = {}, None, []
@@ -728,7 +740,7 @@ def main():
                      and not (c == "mlp_wgrad(all)" and n_prof and split_wg)]
     # one launch of that kernel per step is bracketed (each event pair costs ~40-80 us of wall time)
     dom_calls = sorted(dom_calls, key=lambda c: -breakdown[c][1])[:1]
-    if not dom_calls and not a.no_kernel_timing and stage == "fine":
+    if not dom_calls and n_prof and stage == "fine":
         # too few warm-up steps for the breakdown: bracket the kernel that dominates every profile taken so far
         split_fwd = bool(getattr(eng, "split_fwd", False)) and a.dtype == "f32"
         split_bwd = split_fwd and bool(getattr(eng, "split_bwd", False))
@@ -740,7 +752,7 @@ def main():
 
     # optimizer step, reported separately (outside the named path, never part of `value`)
     opt_ms = None
-    if not a.no_optimizer and stage != "finetune":   # every rank: one() is a collective step when N > 1 (rank 0 reports)
+    if a.full and not a.no_optimizer and stage != "finetune":   # every rank: one() is a collective step when N > 1 (rank 0 reports)
         from esr_nerf_amd.optimizer import create_optimizer_or_freeze_model
         lrs = dict(off_color=0.1, off_rgbnet=0.003, emo_color=0.1, emo_rgbnet=0.003, sdf=0.005, tonemapper=0.003,
                    brdf=0.1, brdfnet=0.003, emitnet=0.003, envmap=0.003)
@@ -759,7 +771,7 @@ def main():
     # the per-step zero-fill of the flat gradient buffer (the reference's dense zeros_like(grid) allocations), timed alone:
     # it is inside every step (on the side stream, beside the march) and grows with the grid
     zero_ms = None
-    if not a.no_optimizer and getattr(step, "_flat", None) is not None:
+    if a.full and not a.no_optimizer and getattr(step, "_flat", None) is not None:
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         for _ in range(5):
@@ -768,7 +780,7 @@ def main():
         zero_ms = (time.perf_counter() - t1) / 5 * 1e3
     # the trainer's every-third-iteration TV lines (fine.py:383-400), reported separately like the optimizer
     tv_ms = None
-    if not a.no_optimizer and stage in ("fine", "lts", "pdra"):
+    if a.full and not a.no_optimizer and stage in ("fine", "lts", "pdra"):
         l_tv, g_tv = one()
         for _ in range(2):
             step.add_regularisers(l_tv, g_tv, n_rays * world, W_TV, TVS, True)
@@ -782,13 +794,13 @@ def main():
     # fixed costs of the brick exchange (HIP events; EVERY rank: the phases contain collectives; with one rank they are
     # local): flags / union / list / pack / all-reduce / unpack -- what the driver's multi-GPU runs can be read against
     phases = None
-    if pg is not None and step is not None and getattr(step, "_flat", None) is not None and not rehearsal:
+    if a.full and pg is not None and step is not None and getattr(step, "_flat", None) is not None and not rehearsal:
         from esr_nerf_amd.grad_sync import GridGradSync
         prof = getattr(step, "_sync", None) or GridGradSync(pg)
         phases = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in prof.profile(step._flat[: step._n_grid]).items()}
 
     sweep = None
-    if (pg is not None and (a.sync_sweep or (2 <= world <= 4 and not a.no_sync_sweep)) and stage != "finetune"
+    if (pg is not None and (a.sync_sweep or (a.full and 2 <= world <= 4 and not a.no_sync_sweep)) and stage != "finetune"
             and getattr(step, "sharded", None) is None):      # (a sharded optimizer forces the shard form: nothing to compare)
         sweep = {}
         keep_mode, keep_sync, keep_used = step._sync_mode, step._sync, getattr(step, "sync_mode_used", None)
@@ -828,7 +840,7 @@ def main():
                             + (" + the TV lines on every third step" if tv_in_step else "") + " (no optimizer step)"
                             + ("" if stage == "fine" else f"; + {getattr(step, 'ltspts', model.num_ltspts)} surface points x {model.num_2ndrays} "
                                f"secondary rays per GPU ({round(sum(c['sec_m3'] for c in prof_counts) / len(prof_counts)) if prof_counts else eng.sec.counts.get('m3')} "
-                               f"surviving secondary samples, mean of the instrumented steps: the draws are random)")
+                               f"surviving secondary samples, {'mean of the instrumented steps' if prof_counts else 'last step'}: the draws are random)")
                             + ("; fine-tune target: edited emission + its light transport, only emo_color / emo_rgbnet "
                                "train" if stage == "finetune" else ""),
                 "rays_per_gpu": n_rays, "samples_per_ray": samples if not a.grid else 128, "surviving_samples": counts.get("m3"),
@@ -1069,15 +1081,15 @@ def main():
         elif pg is not None:
             out["grad_exchange"] = dict(mode="dense-async", dense_grid_mb=round(step._n_grid * 4 / 1e6, 1),
                                         sent_mb=round(step._n_grid * 4 / 1e6, 1))
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             if stage == "fine":
                 out["cpu_baseline"] = cpu_baseline(model, scene, a.s_val, min(a.cpu_rays or n_rays, n_rays), a.cpu_iters)
             elif stage != "finetune":
                 out["cpu_baseline"] = cpu_baseline_lts(model, scene, a.s_val, min(a.cpu_rays or 1024, n_rays), a.cpu_iters,
                                                        stage, cfg.app.trainer)
-        # (only the plain default run: profiling / A-B invocations of the headline workload pass one of the --no-* switches)
-        if headline and world == 1 and not (a.no_other or a.force_dist or a.no_cpu_baseline or a.no_optimizer
-                                            or a.no_kernel_timing or a.no_tv):
+        # (only the --full headline command: profiling / A-B invocations of the headline workload pass one of the --no-* switches)
+        if a.full and headline and world == 1 and not (a.no_other or a.force_dist or a.no_cpu_baseline or a.no_optimizer
+                                                       or a.no_kernel_timing or a.no_tv):
             # the other BASELINE configs, driver-observed: measured AFTER the headline (its fields above are final)
             out["other_workloads"] = other_workloads()
         line = json.dumps(out)

@@ -276,7 +276,7 @@ def test_bench_flow_with_two_ranks_rehearsal(scaling):
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
          "--master-port", "29537", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "2",
-         "--config", "small", "--scaling", scaling],
+         "--config", "small", "--scaling", scaling, "--full"],
         env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -285,6 +285,7 @@ def test_bench_flow_with_two_ranks_rehearsal(scaling):
     assert d["config"]["rays_per_gpu"] == (512 if scaling == "weak" else 256)      # strong: the config's rays in total
     assert d["grad_exchange"]["mode"] == "sparse" and d["grad_exchange"]["bricks"] > 0      # 2 ranks -> sparse
     assert "REHEARSAL" in d["data"]
+    assert {"optimizer_step", "tv_terms", "kernel_ms_per_step_instrumented", "grad_sync_sweep_ms"} <= set(d)   # --full's sections
 
 
 @pytest.mark.parametrize("scaling,stage", [("weak", "fine"), ("strong", "lts")])
@@ -301,7 +302,7 @@ def test_bench_flow_with_the_dense_exchange_rehearsal(scaling, stage):
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=4", "--master-addr", "127.0.0.1",
          "--master-port", "29543", os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
-         "--config", "small", "--stage", stage, "--scaling", scaling, "--sync-sweep", "--no-cpu-baseline", "--no-other"],
+         "--config", "small", "--stage", stage, "--scaling", scaling, "--sync-sweep", "--full", "--no-cpu-baseline", "--no-other"],
         env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -334,7 +335,7 @@ def test_bench_under_rccl_prints_one_json_line_and_nothing_else_on_stdout():
     out = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
          "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-         "--config", "small", "--force-dist", "--no-cpu-baseline", "--no-other", "--no-optimizer"],
+         "--config", "small", "--force-dist", "--full", "--no-cpu-baseline", "--no-other", "--no-optimizer"],
         env=dict(os.environ, OMP_NUM_THREADS="2"), capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, _why(out)
     lines = [l for l in out.stdout.splitlines() if l.strip()]

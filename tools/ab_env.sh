@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B timing of env-selected variants of the step on ONE box (box-to-box spread is ~2 %, larger than most single changes):
 #   gpurun -- 'bash tools/ab_env.sh <tag> "VAR=a VAR2=b" "VAR=c" ... [-- bench args]'
-# every variant: bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-optimizer; prints ms/step and the kernel breakdown
+# every variant: bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-optimizer; prints ms/step and the kernel breakdown
 TAG=$1; shift
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$ROOT"; mkdir -p gpurun_out
@@ -10,7 +10,7 @@ while [ $# -gt 0 ]; do if [ "$1" == "--" ]; then shift; ARGS=("$@"); break; fi; 
 i=0
 for v in "${VARS[@]}"; do
   out=gpurun_out/${TAG}_ab_$i.json
-  env $v python3 bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-optimizer "${ARGS[@]}" > $out 2> gpurun_out/${TAG}_ab_$i.err || { echo "variant '$v' failed"; tail -5 gpurun_out/${TAG}_ab_$i.err; }
+  env $v python3 bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-optimizer "${ARGS[@]}" > $out 2> ${out%.json}.err || { echo "variant '$v' failed"; tail -5 ${out%.json}.err; }
   python3 - "$v" $out <<'PY'
 import json, sys
 try:
