@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libesr_hip.so")
 # developer experiments only (python -m esr_nerf_amd.build --variant builds alternative libraries; tools/ab_env.sh times them
 # side by side on one box)
 LIB_PATH = os.environ.get("ESR_LIB_PATH", LIB_PATH)
-ABI_VERSION = 27
+ABI_VERSION = 28
 _lib = None
 
 
@@ -83,6 +83,12 @@ class EsrLtsGrads(C.Structure):
                                           "d_emission", "d_mus", "d_lambdas", "d_lobes")]
 
 
+class EsrCdIndex(C.Structure):           # esr_cd_index_t
+    _fields_ = [("origin", C.c_double * 3), ("h", C.c_double), ("dims", C.c_int32 * 3), ("coarse", C.c_int32),
+                ("cap", C.c_int64), ("keys", C.c_void_p), ("cells", C.c_void_p), ("start", C.c_void_p), ("pts", C.c_void_p),
+                ("ids", C.c_void_p), ("ccap", C.c_int64), ("ckeys", C.c_void_p)]
+
+
 class EsrMlpWeights(C.Structure):
     _fields_ = [("w", C.c_void_p * 4), ("b", C.c_void_p * 4)]
 
@@ -122,6 +128,8 @@ EXPORTS = [
     "esr_brick_floats", "esr_brick_flags", "esr_brick_pack", "esr_brick_unpack", "esr_brick_list", "esr_brick_list_scratch_ints",
     "esr_smooth_grad_tv_fwd", "esr_smooth_grad_tv_bwd", "esr_host_choice_noreplace", "esr_host_choice_start", "esr_host_choice_wait",
     "esr_mesh_field", "esr_mesh_blocks", "esr_mesh_count", "esr_mesh_emit",
+    "esr_cd_sample_count", "esr_cd_sample_fill", "esr_cd_cell_keys", "esr_cd_hash_insert", "esr_cd_downsample_round",
+    "esr_cd_nn",
 ]
 
 
@@ -153,6 +161,10 @@ def lib() -> C.CDLL:
             L.esr_mlp_split_gain_offset.restype = C.c_int64
         if hasattr(L, "esr_mesh_blocks"):
             L.esr_mesh_blocks.restype = C.c_int64
+        for name in ("esr_cd_sample_count", "esr_cd_sample_fill", "esr_cd_cell_keys", "esr_cd_hash_insert",
+                     "esr_cd_downsample_round", "esr_cd_nn"):
+            if hasattr(L, name):
+                getattr(L, name).restype = C.c_int
         if L.esr_abi_version() != ABI_VERSION:
             raise RuntimeError("libesr_hip.so ABI version mismatch: rebuild")
         _lib = L

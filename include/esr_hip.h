@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 27
+#define ESR_ABI_VERSION 28
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -1035,6 +1035,62 @@ int64_t esr_mesh_blocks(int32_t r0, int32_t r1, int32_t r2);
 int esr_mesh_count(const float *u, int32_t r0, int32_t r1, int32_t r2, float threshold, int64_t *counts, void *stream);
 int esr_mesh_emit(const float *u, int32_t r0, int32_t r1, int32_t r2, float threshold, const int64_t *offsets,
                   int32_t *vid, double *vertices, int64_t *triangles, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * H. Chamfer metric (utils2.metric.DTU_CD): triangle sampling, a cell index, the radius downsample, nearest neighbours
+ * ------------------------------------------------------------------------- */
+
+/*
+ * A cell index over a point cloud of n points [host struct, device arrays].  Cell c = floor((p - origin) / h) per axis
+ * (0 <= c < dims, each dims < 2^21), key = cx << 42 | cy << 21 | cz.  pts [n,3] f64 are the points sorted by key (stable);
+ * ids [n] the sort's source index of each; start [n_cells + 1] i64 the range of each unique key; keys [cap] i64 / cells
+ * [cap] i32 the hash table key -> unique-key rank (cap a power of two > the cell count, empty slots -1, filled by
+ * esr_cd_hash_insert).  coarse, ckeys [ccap]: the occupancy table of the cells of coarse^3 fine cells (esr_cd_nn only).
+ */
+typedef struct {
+    double origin[3];
+    double h;
+    int32_t dims[3];
+    int32_t coarse;
+    int64_t cap;
+    const int64_t *keys;
+    const int32_t *cells;
+    const int64_t *start;
+    const double *pts;
+    const int32_t *ids;
+    int64_t ccap;
+    const int64_t *ckeys;
+} esr_cd_index_t;
+
+/*
+ * Points sampled on triangles -- replaces utils2/metric.py:101-165 (sample_single_tri over a multiprocessing pool).
+ * vertices [V,3] f64, triangles [n_tri,3] i64.  esr_cd_sample_count: counts [n_tri] i64 (0 for area2 == 0);
+ * esr_cd_sample_fill: points [sum counts, 3] f64, triangle t's samples from row offsets[t] (the exclusive scan of counts)
+ * in the reference's (i, j) row-major order.  Arithmetic: the header of csrc/chamfer.hip.
+ */
+int esr_cd_sample_count(const double *vertices, const int64_t *triangles, int64_t n_tri, double thresh, int64_t *counts,
+                        void *stream);
+int esr_cd_sample_fill(const double *vertices, const int64_t *triangles, int64_t n_tri, double thresh,
+                       const int64_t *offsets, double *points, void *stream);
+/* keys [n] i64 of points [n,3] f64 under index->origin / h / dims (cells clamped into the box; ESR_ECAP for dims >= 2^21) */
+int esr_cd_cell_keys(const esr_cd_index_t *index, const double *points, int64_t n, int64_t *keys, void *stream);
+/* inserts the n_u distinct ukeys into table_keys [cap] (pre-filled with -1), table_vals [cap] = the key's rank (or NULL) */
+int esr_cd_hash_insert(const int64_t *ukeys, int64_t n_u, int64_t cap, int64_t *table_keys, int32_t *table_vals,
+                       void *stream);
+/*
+ * One round of the radius downsample -- replaces utils2/metric.py:168-187 (radius_neighbors + the keep loop).  points
+ * [n,3] f64 in the order; the index is built over the same points with h >= thresh and ids = the order rank.  state [n]
+ * i8: 0 undecided, 1 kept, 2 removed (start all 0); point k becomes removed when a kept earlier point lies within thresh
+ * (((dx*dx + dy*dy) + dz*dz) <= thresh*thresh) and kept when every earlier point within thresh is removed.  Sets
+ * changed[0] = 1 when a state changed; rounds until one changes nothing give the sequential loop's mask exactly.
+ */
+int esr_cd_downsample_round(const esr_cd_index_t *index, const double *points, int64_t n, double thresh, int8_t *state,
+                            int32_t *changed, void *stream);
+/*
+ * Nearest-neighbour distances -- replaces the kd-tree kneighbors passes of utils2/metric.py:209-231.  queries [nq,3] f64;
+ * dist [nq] f64 = sqrt(min squared distance to the index's points), +inf when that is not < max_dist.
+ */
+int esr_cd_nn(const esr_cd_index_t *index, const double *queries, int64_t nq, double max_dist, double *dist, void *stream);
 
 #ifdef __cplusplus
 }
