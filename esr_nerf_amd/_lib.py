@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libesr_hip.so")
 # developer experiments only (python -m esr_nerf_amd.build --variant builds alternative libraries; tools/ab_env.sh times them
 # side by side on one box)
 LIB_PATH = os.environ.get("ESR_LIB_PATH", LIB_PATH)
-ABI_VERSION = 28
+ABI_VERSION = 29
 _lib = None
 
 
@@ -89,6 +89,27 @@ class EsrCdIndex(C.Structure):           # esr_cd_index_t
                 ("ids", C.c_void_p), ("ccap", C.c_int64), ("ckeys", C.c_void_p)]
 
 
+class EsrDvgo(C.Structure):             # esr_dvgo_t
+    _fields_ = [("density", C.c_void_p), ("off_color", C.c_void_p), ("emo_color", C.c_void_p), ("dims", C.c_int32 * 3),
+                ("xyz_min", C.c_float * 3), ("xyz_max", C.c_float * 3)] + \
+               [(n, C.c_float) for n in ("near_", "far_", "step_scale", "interval", "act_shift")] + [("n_samples", C.c_int32)]
+
+
+class EsrDvgoRays(C.Structure):         # esr_dvgo_rays_t
+    _fields_ = [(n, C.c_void_p) for n in ("rays_o", "rays_d", "nrm", "jitter", "em_modes")] + \
+               [("em_all", C.c_int32), ("n_rays", C.c_int64)]
+
+
+class EsrDvgoOut(C.Structure):          # esr_dvgo_out_t
+    _fields_ = [(n, C.c_void_p) for n in ("alpha", "alphainv_cum", "weights", "raw_rgb", "rgb", "depth", "disp", "white_bg",
+                                          "off_rgb", "on_rgb", "emo_rgb")]
+
+
+class EsrDvgoBwd(C.Structure):          # esr_dvgo_bwd_t
+    _fields_ = [(n, C.c_void_p) for n in ("alpha", "alphainv_cum", "raw_rgb", "g_alphainv_cum", "g_weights", "g_raw_rgb",
+                                          "g_rgb", "grad_density", "grad_off", "grad_emo")]
+
+
 class EsrMlpWeights(C.Structure):
     _fields_ = [("w", C.c_void_p * 4), ("b", C.c_void_p * 4)]
 
@@ -130,6 +151,7 @@ EXPORTS = [
     "esr_mesh_field", "esr_mesh_blocks", "esr_mesh_count", "esr_mesh_emit",
     "esr_cd_sample_count", "esr_cd_sample_fill", "esr_cd_cell_keys", "esr_cd_hash_insert", "esr_cd_downsample_round",
     "esr_cd_nn",
+    "esr_dvgo_fwd", "esr_dvgo_eval", "esr_dvgo_bwd", "esr_dvgo_count", "esr_dvgo_count_add",
 ]
 
 

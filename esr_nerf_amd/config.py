@@ -73,6 +73,20 @@ COARSE_MODEL = dict(mask_ks=3, maskcache_thres=0.001, fastcolor_thres=0.0001, st
 COARSE_TRAINER = dict(weight_entropy_last=0.001, weight_tv_density=0.001, weight_tv_color=0.01,
                       tvs=dict(sdf=0.1, smooth_grad=0.05), s_start=5.0, s_inv_ratio=50.0)
 
+# /root/reference/cfg/app/alphamask.yaml:12-42 (model, batch size, learning rates, loss weights)
+ALPHAMASK_MODEL = dict(num_voxels=1024000, stepsize=0.5, alpha_init=0.000001)
+ALPHAMASK_TRAINER = dict(batch_size=8192, n_iters=10000, lrs=dict(density=0.1, off_color=0.1, emo_color=0.1), lr_decay=20,
+                         weight_entropy_last=0.01, weight_rgbper=0.1)
+
+
+def alphamask_cfg(device: str = "cpu", **model_over) -> AttrDict:
+    return AttrDict(
+        system=dict(device=device, debug=True, seed=0, tqdm_iters=10),
+        app=dict(model=dict(ALPHAMASK_MODEL, **model_over), trainer=dict(ALPHAMASK_TRAINER)),
+        data=dict(white_bg=True),
+        global_step=0,
+    )
+
 
 def coarse_cfg(device: str = "cpu", **model_over) -> AttrDict:
     m = dict(COARSE_MODEL)

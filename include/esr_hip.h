@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 28
+#define ESR_ABI_VERSION 29
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -1091,6 +1091,91 @@ int esr_cd_downsample_round(const esr_cd_index_t *index, const double *points, i
  * dist [nq] f64 = sqrt(min squared distance to the index's points), +inf when that is not < max_dist.
  */
 int esr_cd_nn(const esr_cd_index_t *index, const double *queries, int64_t nq, double max_dist, double *dist, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * I. DVGO pre-stage (app/coarse/model/dvgo.py, the alphamask renderer)
+ * ------------------------------------------------------------------------- */
+
+/*
+ * The model [host struct, device grids]: density [1,X,Y,Z], off_color and emo_color [3,X,Y,Z] (channels first, as the
+ * nn.Parameters); xyz_min / xyz_max the box; step_scale = stepsize * voxel_size rounded as torch rounds it (float32);
+ * interval = stepsize; n_samples = the model's N_samples (S).
+ */
+typedef struct {
+    const float *density;
+    const float *off_color;
+    const float *emo_color;
+    int32_t dims[3];
+    float xyz_min[3];
+    float xyz_max[3];
+    float near_, far_, step_scale, interval, act_shift;
+    int32_t n_samples;
+} esr_dvgo_t;
+
+/*
+ * The rays [host struct, device arrays]: rays_o, rays_d [n,3]; nrm [n] = rays_d.norm(dim=-1) (torch's); jitter [n] the
+ * training draw u (NULL: none); em_modes [n] int32 (NULL: every ray is em_all).
+ */
+typedef struct {
+    const float *rays_o;
+    const float *rays_d;
+    const float *nrm;
+    const float *jitter;
+    const int32_t *em_modes;
+    int32_t em_all;
+    int64_t n_rays;
+} esr_dvgo_rays_t;
+
+/*
+ * Outputs [host struct, device arrays].  Training (esr_dvgo_fwd): alpha [n,S] (kept for the backward), alphainv_cum
+ * [n,S+1], weights [n,S], raw_rgb [n,S,3], rgb [n,3].  Evaluation (esr_dvgo_eval): alpha [n,S] scratch, depth, disp [n],
+ * white_bg [n], off_rgb, on_rgb, emo_rgb [n,3] (rgb is off_rgb or on_rgb: the caller picks).
+ */
+typedef struct {
+    float *alpha;
+    float *alphainv_cum;
+    float *weights;
+    float *raw_rgb;
+    float *rgb;
+    float *depth;
+    float *disp;
+    float *white_bg;
+    float *off_rgb;
+    float *on_rgb;
+    float *emo_rgb;
+} esr_dvgo_out_t;
+
+/*
+ * Backward of esr_dvgo_fwd [host struct, device arrays]: alpha, alphainv_cum, raw_rgb as the forward wrote them; the
+ * upstream gradients g_alphainv_cum [n,S+1], g_weights [n,S], g_raw_rgb [n,S,3], g_rgb [n,3] (each may be NULL: zero);
+ * grad_density [X,Y,Z], grad_off, grad_emo [3,X,Y,Z] are ADDED to (float atomics: the caller zeroes them).
+ */
+typedef struct {
+    const float *alpha;
+    const float *alphainv_cum;
+    const float *raw_rgb;
+    const float *g_alphainv_cum;
+    const float *g_weights;
+    const float *g_raw_rgb;
+    const float *g_rgb;
+    float *grad_density;
+    float *grad_off;
+    float *grad_emo;
+} esr_dvgo_bwd_t;
+
+/*
+ * forward_training / forward_evaluate -- replaces dvgo.py:140-263 (sample_ray, grid_sampler, activate_density,
+ * get_ray_marching_ray and the colour sums).  Arithmetic and mapping: the header of csrc/dvgo.hip.
+ */
+int esr_dvgo_fwd(const esr_dvgo_t *model, const esr_dvgo_rays_t *rays, const esr_dvgo_out_t *out, void *stream);
+int esr_dvgo_eval(const esr_dvgo_t *model, const esr_dvgo_rays_t *rays, const esr_dvgo_out_t *out, void *stream);
+int esr_dvgo_bwd(const esr_dvgo_t *model, const esr_dvgo_rays_t *rays, const esr_dvgo_bwd_t *bwd, void *stream);
+/*
+ * voxel_count_views, one view -- replaces dvgo.py:59-93.  sum [X,Y,Z] (zeroed by the caller) += the trilinear weights of
+ * the S unjittered, unmasked samples of every ray; esr_dvgo_count_add: count[i] += sum[i] > 1.
+ */
+int esr_dvgo_count(const esr_dvgo_t *model, const esr_dvgo_rays_t *rays, float *sum, void *stream);
+int esr_dvgo_count_add(const float *sum, int64_t n, float *count, void *stream);
 
 #ifdef __cplusplus
 }
