@@ -586,6 +586,9 @@ int launch_march(MarchParams &P, hipStream_t s)
     int wpb = 4;
     while (wpb > 1 && per_wave * wpb > 64 * 1024) wpb >>= 1;
     if (per_wave * wpb > 160 * 1024) return ESR_ECAP;
+    // a cap whose backward (5 arrays, + 1 in "grad" mode) cannot be launched is refused by the forward passes too: a step
+    // then fails before its forward instead of at its backward
+    if ((size_t)(5 + (GA ? 1 : 0)) * P.cap * sizeof(float) > 160 * 1024) return ESR_ECAP;
     static std::atomic<uint64_t> optin{0};             // one wave per block beyond 64 KB (cap > ~3.2k steps in BWD mode)
     if (int rc = esr_lds_optin(reinterpret_cast<const void *>(&march_kernel<MODE, COARSE, GA>), per_wave * wpb, optin)) return rc;
     const int grid = (P.n_rays + wpb - 1) / wpb;

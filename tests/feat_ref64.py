@@ -93,23 +93,40 @@ def _r(x, like=None):
     return x if (like is not None and like.dtype == F64) else x.to(F32)
 
 
+def ray_geom(rays_o, rays_d, lo, hi, near, stepdist):
+    """esr_ray_geom (esr_common.h, far = 1e9) per ray, binary32: start [N,3], unit direction [N,3] and n_steps [N] int64."""
+    o, d = rays_o.double(), rays_d.double()
+    lo, hi = lo.double(), hi.double()
+    v = torch.where(d == 0, _f(1e-6).double(), d)
+    ta, tb = _r(_r(hi - o).double() / v).double(), _r(_r(lo - o).double() / v).double()
+    mn, mx = torch.minimum(ta, tb), torch.maximum(ta, tb)
+    lo_t = torch.maximum(torch.maximum(mn[:, 0], mn[:, 1]), mn[:, 2])
+    hi_t = torch.minimum(torch.minimum(mx[:, 0], mx[:, 1]), mx[:, 2])
+    far, nr = _f(1e9).double(), _f(near).double()
+    tmin = torch.maximum(torch.minimum(lo_t, far), nr)
+    tmax = torch.maximum(torch.minimum(hi_t, far), nr)
+    sq = lambda a: _r(a * a).double()
+    nrm = _r(torch.sqrt(_r(_r(sq(d[:, 0]) + sq(d[:, 1])).double() + sq(d[:, 2])).double())).double()
+    length = _r(_r(_r(tmax - tmin).double() * nrm).double() / _f(stepdist).double())
+    n_steps = torch.ceil(length).double().clamp_min(1.0).long()
+    start = _r(o + _r(d * tmin[:, None]).double())
+    dirv = _r(d / nrm[:, None])
+    return start, dirv, n_steps
+
+
+def ray_point(start, dirv, stepdist, step):
+    """esr_ray_point, binary32: sample `step` [M] of rays with start / dirv [M,3]."""
+    dist = _r(_f(stepdist).double() * step.double()).double()
+    return _r(start.double() + _r(dirv.double() * dist[:, None]).double())
+
+
 def record_points(case: Case):
     """esr_ray_geom + esr_ray_point (esr_common.h) per record: positions [tiles*32, 3] float32 and the valid mask."""
     r = case.rec_ray.long()
     valid = r >= 0
-    o, d = case.rays_o[r.clamp_min(0)].double(), case.rays_d[r.clamp_min(0)].double()
-    lo, hi = case.lo.double(), case.hi.double()
-    v = torch.where(d == 0, _f(1e-6).double(), d)
-    ta, tb = _r(_r(hi - o).double() / v).double(), _r(_r(lo - o).double() / v).double()
-    mn = torch.minimum(ta, tb)
-    lo_t = torch.maximum(torch.maximum(mn[:, 0], mn[:, 1]), mn[:, 2])
-    tmin = torch.maximum(torch.minimum(lo_t, _f(1e9).double()), _f(case.near).double())
-    sq = lambda a: _r(a * a).double()
-    nrm = _r(torch.sqrt(_r(_r(sq(d[:, 0]) + sq(d[:, 1])).double() + sq(d[:, 2])).double())).double()
-    start = _r(o + _r(d * tmin[:, None]).double()).double()
-    dirv = _r(d / nrm[:, None]).double()
-    dist = _r(_f(case.stepdist).double() * case.rec_step.double()).double()
-    p = _r(start + _r(dirv * dist[:, None]).double())
+    start, dirv, _ = ray_geom(case.rays_o[r.clamp_min(0)], case.rays_d[r.clamp_min(0)], case.lo, case.hi, case.near,
+                              case.stepdist)
+    p = ray_point(start, dirv, case.stepdist, case.rec_step)
     return torch.where(valid[:, None], p, torch.zeros_like(p)), valid
 
 
