@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libesr_hip.so")
 # developer experiments only (python -m esr_nerf_amd.build --variant builds alternative libraries; tools/ab_env.sh times them
 # side by side on one box)
 LIB_PATH = os.environ.get("ESR_LIB_PATH", LIB_PATH)
-ABI_VERSION = 29
+ABI_VERSION = 30
 _lib = None
 
 
@@ -110,6 +110,13 @@ class EsrDvgoBwd(C.Structure):          # esr_dvgo_bwd_t
                                           "g_rgb", "grad_density", "grad_off", "grad_emo")]
 
 
+class EsrViewPost(C.Structure):         # esr_view_post_t
+    _fields_ = [("v", C.c_void_p), ("wbg", C.c_void_p), ("wbg_scale", C.c_float), ("lin", C.c_int32), ("n", C.c_int64),
+                ("channels", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("out", "gamma", "out_u8", "gamma_u8", "target_out", "target_gamma", "partials",
+                                          "sqerr")]
+
+
 class EsrMlpWeights(C.Structure):
     _fields_ = [("w", C.c_void_p * 4), ("b", C.c_void_p * 4)]
 
@@ -152,6 +159,7 @@ EXPORTS = [
     "esr_cd_sample_count", "esr_cd_sample_fill", "esr_cd_cell_keys", "esr_cd_hash_insert", "esr_cd_downsample_round",
     "esr_cd_nn",
     "esr_dvgo_fwd", "esr_dvgo_eval", "esr_dvgo_bwd", "esr_dvgo_count", "esr_dvgo_count_add",
+    "esr_ssim", "esr_view_post", "esr_sqerr_sum", "esr_gamma_curve", "esr_mask_iou",
 ]
 
 
@@ -184,7 +192,8 @@ def lib() -> C.CDLL:
         if hasattr(L, "esr_mesh_blocks"):
             L.esr_mesh_blocks.restype = C.c_int64
         for name in ("esr_cd_sample_count", "esr_cd_sample_fill", "esr_cd_cell_keys", "esr_cd_hash_insert",
-                     "esr_cd_downsample_round", "esr_cd_nn"):
+                     "esr_cd_downsample_round", "esr_cd_nn", "esr_ssim", "esr_view_post", "esr_sqerr_sum", "esr_gamma_curve",
+                     "esr_mask_iou"):
             if hasattr(L, name):
                 getattr(L, name).restype = C.c_int
         if L.esr_abi_version() != ABI_VERSION:

@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 29
+#define ESR_ABI_VERSION 30
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -1176,6 +1176,57 @@ int esr_dvgo_bwd(const esr_dvgo_t *model, const esr_dvgo_rays_t *rays, const esr
  */
 int esr_dvgo_count(const esr_dvgo_t *model, const esr_dvgo_rays_t *rays, float *sum, void *stream);
 int esr_dvgo_count_add(const float *sum, int64_t n, float *count, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * J. Image-level evaluation metrics (utils2/metric.py rgb_ssim / IoU, the view post-processing of app/fine/fine.py:572-605)
+ * ------------------------------------------------------------------------- */
+
+#define ESR_SSIM_MAX_TAPS 33     /* largest filter_size of esr_ssim (ESR_ECAP beyond it: the tile's LDS image)          */
+#define ESR_METRICS_BLOCKS 1024  /* most workgroups of a metrics launch = doubles per `partials` sum                    */
+
+/*
+ * rgb_ssim -- replaces utils2/metric.py:31-88.  img0, img1 [H,W,3] f32; taps [host] the filter_size float64 filter
+ * weights (metric.py:47-51); c1 = (k1 max_val)^2, c2 = (k2 max_val)^2.  map (or NULL) [H-fs+1, W-fs+1, 3] f64;
+ * partials [ESR_METRICS_BLOCKS] f64 scratch; mean [1] f64 = the mean of the map.  One fused launch plus a one-workgroup
+ * sum of the partials: no float atomics, the same bits on every call.  ESR_EINVAL for H or W < filter_size.
+ * Arithmetic (float32 products, float64 behind them): the header of csrc/metrics.hip.
+ */
+int esr_ssim(const float *img0, const float *img1, int32_t H, int32_t W, const double *taps, int32_t filter_size, double c1,
+             double c2, double *map, double *partials, double *mean, void *stream);
+
+/*
+ * One result image of a view [host struct, device arrays] -- replaces fine.py:572-587, the uint8 images of :611-617 and
+ * the F.mse_loss calls of :596-601.  v [n,channels] f32 (channels 1 or 3), wbg [n] f32 or NULL (no background term):
+ *   s = v + wbg * wbg_scale
+ *   lin == 0: out = clamp(s, 0, 1)
+ *   lin != 0: out = max(s, 0); gamma = apply_gamma_curve(clamp(s, 0, 1)) (utils2/image.py:14-26, float32)
+ * out may be v.  out_u8 / gamma_u8 (or NULL) = (uint8)(clamp01(.) * 255) of the float written beside it.  target_out /
+ * target_gamma (or NULL) [n,channels] f32: sqerr[0] / sqerr[1] (f64) = the sum over all elements of
+ * ((double)out - (double)target)^2, deterministic; partials [2 * ESR_METRICS_BLOCKS] f64 scratch (needed with a target).
+ */
+typedef struct {
+    const float *v;
+    const float *wbg;
+    float wbg_scale;
+    int32_t lin;
+    int64_t n;
+    int32_t channels;
+    float *out;
+    float *gamma;
+    uint8_t *out_u8;
+    uint8_t *gamma_u8;
+    const float *target_out;
+    const float *target_gamma;
+    double *partials;
+    double *sqerr;
+} esr_view_post_t;
+int esr_view_post(const esr_view_post_t *job, void *stream);
+/* sum [1] f64 = sum_i ((double)a[i] - (double)b[i])^2, a, b [n] f32; partials [ESR_METRICS_BLOCKS] f64 scratch */
+int esr_sqerr_sum(const float *a, const float *b, int64_t n, double *partials, double *sum, void *stream);
+/* y = apply_gamma_curve(x) (utils2/image.py:14-26), x, y [n] f32 */
+int esr_gamma_curve(const float *x, int64_t n, float *y, void *stream);
+/* IoU counts -- replaces utils2/metric.py:95-98.  mask1, mask2 [n] u8 / bool; counts [2] i64 = |m1 & m2|, |m1 | m2| */
+int esr_mask_iou(const uint8_t *mask1, const uint8_t *mask2, int64_t n, int64_t *counts, void *stream);
 
 #ifdef __cplusplus
 }

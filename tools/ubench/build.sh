@@ -3,7 +3,7 @@
 #   ./tools/ubench/lds_atomic   etc.
 cd "$(dirname "$0")"
 # standalone: no product source included
-for f in lds_atomic lds_dma_m0 mfma_f32_loop mfma_vmem_mix mfma4_loop mfma_mix permlane_swap mfma_f32_shapes mfma_valu_overlap issue_cost asm_behind_mfma reg_canary gather_width; do
+for f in lds_atomic lds_dma_m0 fma_f64_loop mfma_f32_loop mfma_vmem_mix mfma4_loop mfma_mix permlane_swap mfma_f32_shapes mfma_valu_overlap issue_cost asm_behind_mfma reg_canary gather_width; do
   /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -o $f $f.hip 2>&1 | grep -E "error"
 done
 # the stamp harnesses include a product kernel source: compiled with the product's flags for that source
