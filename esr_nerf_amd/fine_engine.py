@@ -55,52 +55,86 @@ _RANGE_FLAGS = {}          # device -> the split kernels' sticky range flag (Fin
 
 
 @dataclass
-class FineCtx:
-    """What the backward needs from the forward of one step."""
+class March:
+    """One march through ``FineEngine._march_plan``: what the fill, the feature kernels and the backward need from it."""
     scene: _lib.EsrScene
-    n_rays: int
-    tiles_on: int
-    tiles_all: int
-    counts: Dict[str, int]
+    variant: str                      # "cached" (one walk per step: the count pass records every mask-cache survivor, fill
+    #                                   copies, the backward starts at its scan) or "ga" (cfg neus_alpha "grad": the entry points
+    #                                   that take the rays' view directions; no cache: the gradient taps are not recorded)
+    n: int
     rays_o: torch.Tensor
     rays_d: torch.Tensor
-    viewdirs: torch.Tensor
-    off3: torch.Tensor
+    viewdirs: Optional[torch.Tensor]
     mask_density: torch.Tensor
     sdf: torch.Tensor
+    cnt3: torch.Tensor
+    off3: torch.Tensor
+    stats: torch.Tensor
+    last: torch.Tensor
+    cache: Optional[torch.Tensor] = None
+    tiles_on: int = 0
+    tiles_all: int = 0
+    counts: Dict[str, int] = None
+    e_pre: object = None              # the side stream's event behind ``prelude()``: the main stream waits for it before the
+    #                                   first consumer
+
+
+@dataclass
+class FineCtx:
+    """What the backward needs from the forward of one step."""
+    march: March
     feat_args: object = None
-    march_cache: object = None        # (ray_stats, alphainv_last, cache) of the count pass, for the backward
     x16: bool = False                 # the features of this step are the bf16 tile (ws["X16"]), not the fp32 one
     f32_only: bool = False            # the forward ran on the f32 MFMA kernels (range fallback): so must the backward
+    counts = property(lambda self: self.march.counts)
+
+
+FINE_ROWS = dict(X=X_ROWS, gnorm=4, H0=HID, H1=HID, H2=HID, z_off=4, z_emo=4, lin=4, Xt=XT_ROWS, Ht=HID,
+                 zt=4, rgb=4, dzt=4, dZt=HID, dXt=DX_ROWS, dz=4, dZ0=HID, dZ1=HID, dZ2=HID, dX=DX_ROWS,
+                 dweight=1, rec_w=1, rec_sdf=1, dsdf=1)
+# name -> (elements per tile, dtype): ReLU sign bits [tiles, 3, 64] u32, the record arrays, the bf16 input tile (esr_fine_feat_fwd_x16)
+FINE_OTHER = dict(M0=(192, torch.int32), M1=(192, torch.int32), M2=(192, torch.int32), Mt=(192, torch.int32),
+                  rec_ray=(32, torch.int32), rec_step=(32, torch.int32), X16=(26 * 256, torch.uint8))
 
 
 class _Workspace:
-    """Grow-only device buffers, tile-major [tiles, rows, 32] fp32."""
+    """Grow-only device buffers, tile-major: ``rows`` name -> rows of [tiles, rows, 32] fp32, ``other`` name -> (elements per
+    tile, dtype).  ``ensure`` / ``rec`` / ``rec_ray_now`` / ``ray_buf`` / ``cache`` / ``min_tiles`` are what
+    ``FineEngine._march_plan`` asks of a workspace (lts_engine.Pass offers the same)."""
+    min_tiles = 0                     # nothing is allocated for a march without survivors
 
-    def __init__(self, device):
-        self.device = device
+    def __init__(self, device, rows=FINE_ROWS, other=FINE_OTHER):
+        self.device, self.rows, self.other = device, rows, other
         self.cap_tiles = 0
         self.buf: Dict[str, torch.Tensor] = {}
-
-    ROWS = dict(X=X_ROWS, gnorm=4, H0=HID, H1=HID, H2=HID, z_off=4, z_emo=4, lin=4, Xt=XT_ROWS, Ht=HID,
-                zt=4, rgb=4, dzt=4, dZt=HID, dXt=DX_ROWS, dz=4, dZ0=HID, dZ1=HID, dZ2=HID, dX=DX_ROWS,
-                dweight=1, rec_w=1, rec_sdf=1, dsdf=1)
+        self.ray_bufs: Dict[int, Dict[str, torch.Tensor]] = {}
+        self.cache = None             # the march cache (count -> fill -> backward share one walk), grow-only
 
     def ensure(self, tiles: int):
         if tiles <= self.cap_tiles:
             return
         cap = int(max(tiles, self.cap_tiles) * 1.25) + 64          # (headroom from the first allocation on: lts_engine.Pass.ensure)
-        self.buf = {k: torch.empty(cap * r * 32, dtype=torch.float32, device=self.device)
-                    for k, r in self.ROWS.items()}
-        for k in ("M0", "M1", "M2", "Mt"):          # ReLU sign bits, [tiles, 3, 64] u32
-            self.buf[k] = torch.empty(cap * 3 * 64, dtype=torch.int32, device=self.device)
-        self.buf["rec_ray"] = torch.empty(cap * 32, dtype=torch.int32, device=self.device)
-        self.buf["rec_step"] = torch.empty(cap * 32, dtype=torch.int32, device=self.device)
-        self.buf["X16"] = torch.empty(cap * 26 * 256, dtype=torch.uint8, device=self.device)      # bf16 input tile (esr_fine_feat_fwd_x16)
+        self.buf = {k: torch.empty(cap * r * 32, dtype=torch.float32, device=self.device) for k, r in self.rows.items()}
+        for k, (per_tile, dtype) in self.other.items():
+            self.buf[k] = torch.empty(cap * per_tile, dtype=dtype, device=self.device)
         self.cap_tiles = cap
 
     def __getitem__(self, k):
         return self.buf[k]
+
+    def rec_ray_now(self):
+        return self.buf.get("rec_ray")
+
+    def rec(self):
+        """The four record arrays of the march (after ``ensure``)."""
+        return self.buf["rec_ray"], self.buf["rec_step"], self.buf["rec_w"], self.buf["rec_sdf"]
+
+    def ray_buf(self, n):
+        """Per-ray buffers of a march of ``n`` rays, kept and reused from step to step."""
+        if n not in self.ray_bufs:
+            self.ray_bufs[n] = {k: torch.empty(n * w, dtype=torch.int32, device=self.device)
+                                for k, w in (("cnt3", 1), ("off3", 1), ("stats", 3))}
+        return self.ray_bufs[n]
 
 
 # (module-level classes: a class defined inside the method that returns it is a new TYPE per call -- a type is a reference
@@ -162,7 +196,6 @@ class FineEngine:
         self.packed = {
             k: torch.empty(self.L.esr_mlp_packed_floats(kind), dtype=torch.float32, device=self.device)
             for k, kind in (("off", KIND_RADIANCE), ("emo", KIND_RADIANCE), ("tone", KIND_TONEMAP))}
-        self.ray_bufs: Dict[int, Dict[str, torch.Tensor]] = {}
         self.wgrad_scratch = torch.empty(self.L.esr_mlp_wgrad_scratch_floats(), dtype=torch.float32,
                                          device=self.device)
         self._timing = False
@@ -336,27 +369,115 @@ class FineEngine:
             out[name] = (n + 1, ms + e0.elapsed_time(e1))
         return out
 
-    def _march(self, name, which, sp, rays_o, rays_d, viewdirs, *rest):
-        """One of the three march entry points; with ``neus_grad`` (cfg neus_alpha: "grad") the variants that take the
-        batch's view directions."""
-        if self.neus_grad:
-            fn = getattr(self.L, f"esr_fine_march_{which}_ga")
-            self._run(name, fn, sp, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(viewdirs), *rest)
-        else:
-            self._run(name, getattr(self.L, f"esr_fine_march_{which}"), sp, _lib.ptr(rays_o), _lib.ptr(rays_d), *rest)
+    # -- the march: one owner of the entry-point choice, one of the count -> plan -> fill protocol ------------------------------
+    def _march_launch(self, name, which, m: March, s, *tail, cached=True):
+        """THE place that picks a march entry point, for count, fill and backward alike.  ``tail``: the call's own arguments
+        behind the rays, the fields and ``n`` (count: the plan header; fill: the four record arrays; bwd: dweight, dlast,
+        grad_sdf[, dsdf, acc]).  ``cached=False``: a fresh walk although the march has a cache."""
+        L, p = self.L, _lib.ptr
+        sp, o, d = C.byref(m.scene), p(m.rays_o), p(m.rays_d)
+        if cached and m.variant == "cached":
+            if which == "count":
+                self._run(name, L.esr_fine_march_count_cached, sp, o, d, p(m.mask_density), p(m.sdf), m.n, p(m.cnt3), p(m.last),
+                          p(m.stats), *tail, p(m.cache), s)
+            elif which == "fill":
+                self._run(name, L.esr_fine_march_fill_cached, sp, o, d, m.n, p(m.off3), p(m.stats), p(m.cache), *tail, s)
+            else:
+                self._run(name, L.esr_fine_march_bwd_cached, sp, o, d, m.n, p(m.off3), p(m.stats), p(m.last), p(m.cache), *tail, s)
+            return
+        ga = m.variant == "ga"
+        rays = (sp, o, d, p(m.viewdirs)) if ga else (sp, o, d)
+        own = (p(m.cnt3), p(m.last), p(m.stats)) if which == "count" else (p(m.off3),)
+        self._run(name, getattr(L, f"esr_fine_march_{which}" + ("_ga" if ga else "")), *rays, p(m.mask_density), p(m.sdf), m.n,
+                  *own, *tail, s)
 
-    def _ray_buf(self, n, scene=None):
-        if n not in self.ray_bufs:
-            self.ray_bufs[n] = dict(
-                cnt3=torch.empty(n, dtype=torch.int32, device=self.device),
-                off3=torch.empty(n, dtype=torch.int32, device=self.device),
-                stats=torch.empty(n * 3, dtype=torch.int32, device=self.device))
-        rb = self.ray_bufs[n]
-        if scene is not None:       # march cache (count -> fill -> backward share one walk): sized by the scene's step bound
-            need = int(self.L.esr_fine_march_cache_floats(C.byref(scene), n))
-            if rb.get("cache") is None or rb["cache"].numel() < need:
-                rb["cache"] = torch.empty(need, dtype=torch.float32, device=self.device)
-        return rb
+    def _march_bwd(self, name, m: March, dweight, dlast, grad_sdf, dsdf, acc, s, walk=False):
+        """Backward of one march.  Cached form: the value-tap gradients of the recorded samples go to ``dsdf`` (the
+        feature backward folds them into its SDF window).  neus_alpha "grad", or ``walk``: a fresh walk that scatters every
+        tap straight into ``grad_sdf`` (``dsdf`` is left untouched).  Returns whether ``dsdf`` was written."""
+        g = (_lib.ptr(dweight), _lib.ptr(dlast), _lib.ptr(grad_sdf))
+        if walk or m.variant != "cached":
+            self._march_launch(name, "bwd", m, s, *g, cached=False)
+            return False
+        self._march_launch(name, "bwd", m, s, *g, _lib.ptr(dsdf), acc)
+        return dsdf is not None
+
+    def _plan_header(self):
+        """The plan header in pinned host memory (after the wait for its copy) -> (tiles_on, tiles_all, counts)."""
+        n_on, n_off, _, _, m0, m1, m2, overflow = [int(v) for v in self.plan_host.tolist()]
+        tiles_on = (n_on + 31) // 32                                # (esr_fine_plan_totals leaves the tile counts to the host)
+        if overflow & 1:                                            # (bit 1: the split kernels' range flag, informational)
+            self._overflow()
+        return tiles_on, tiles_on + (n_off + 31) // 32, dict(m0=m0, m1=m1, m2=m2, m3=n_on + n_off, n_on=n_on, n_off=n_off)
+
+    def _march_plan(self, ws, scene, rays_o, rays_d, viewdirs, em_modes, mask_density, sdf, plan_dev=None, prelude=None,
+                    between=None, tag="") -> March:
+        """count -> plan -> (host reads the plan header) -> fill, into the record arrays of ``ws`` (a _Workspace or an
+        lts_engine.Pass).  ``viewdirs``: the rays' view directions -- read under cfg neus_alpha "grad" (esrnerf.py:197-200:
+        every march of the renderer extrapolates its section SDFs along them; the secondary rays' view directions are their
+        own directions, esrnerf.py:575-591).  ``plan_dev``: a zeroed header of the caller's (the fine step carves it out of its
+        one zero fill); without it the engine's persistent one, cleared by ``esr_fine_plan_begin``.
+        ``prelude()``: enqueues work that does not depend on the march (weight packing, zeroing the gradient buffer).
+        It is called between the plan kernel and the host's wait for the plan header, on a SIDE stream: the device has
+        work while the host reads the survivor counts and enqueues the rest of the step, and these bandwidth-bound
+        kernels then run beside the march / feature kernels (gather latency) instead of in front of them
+        (tools/trace_step.py); the main stream must wait for the returned ``e_pre`` before the first consumer.
+        ``between()``: work for the MAIN stream that does not need the march's result, enqueued behind the plan's copy: the
+        device runs it while the host reads the plan and enqueues the fill (otherwise it idles for the host's wake-up + first
+        launches, ~0.1 ms).  ``tag``: suffix of the march launches' names."""
+        L, s = self.L, self._s()
+        n = rays_o.shape[0]
+        variant = "ga" if self.neus_grad else "cached"
+        if variant == "ga":
+            if viewdirs is None:
+                raise RuntimeError("neus_alpha='grad' marches need the rays' view directions")
+            viewdirs = viewdirs.contiguous()
+        rb = ws.ray_buf(n)
+        m = March(scene=scene, variant=variant, n=n, rays_o=rays_o, rays_d=rays_d, viewdirs=viewdirs, mask_density=mask_density,
+                  sdf=sdf, cnt3=rb["cnt3"], off3=rb["off3"], stats=rb["stats"],
+                  last=torch.empty(n, dtype=torch.float32, device=self.device))
+        if variant == "cached":                 # sized by the scene's step bound, grow-only
+            need = int(L.esr_fine_march_cache_floats(C.byref(scene), n))
+            if ws.cache is None or ws.cache.numel() < need:
+                ws.cache = torch.empty(need, dtype=torch.float32, device=self.device)
+            m.cache = ws.cache
+        if plan_dev is None:
+            plan_dev = self.plan_dev
+            self._run("plan_begin", L.esr_fine_plan_begin, _lib.ptr(plan_dev), s)
+        self._march_launch("march_count" + tag, "count", m, s, _lib.ptr(plan_dev))
+        # the counts the host waits for first (a many-workgroup sum), their copy, THEN the one-workgroup scan of the offsets:
+        # it runs while the host reads the header and enqueues (17 / 48 us off the path to the read-back)
+        self._run("plan_totals", L.esr_fine_plan_totals, _lib.ptr(m.cnt3), _lib.ptr(em_modes), _lib.ptr(m.stats), n,
+                  _lib.ptr(plan_dev), s)
+        self.plan_host.copy_(plan_dev, non_blocking=True)
+        landed = torch.cuda.Event()
+        landed.record()
+        self._run("plan", L.esr_fine_plan_offsets, _lib.ptr(m.cnt3), _lib.ptr(em_modes), n, _lib.ptr(m.off3), _lib.ptr(plan_dev), s)
+        if between is not None:
+            between()
+        if prelude is not None:
+            side = self._side_stream(0)
+            side.wait_event(landed)                                 # (also orders it behind the previous step's readers)
+            with torch.cuda.stream(side):
+                prelude()
+                m.e_pre = torch.cuda.Event()
+                m.e_pre.record(side)
+        # padding lanes of the record arrays carry ray -1: filled BEFORE the wait (whole buffer of the previous step's size),
+        # one dispatch less between the read-back and the first kernel that depends on it
+        pre_rec = ws.rec_ray_now()
+        if pre_rec is not None:
+            pre_rec.fill_(-1)
+        landed.synchronize()                                        # the one host wait of the step
+        m.tiles_on, m.tiles_all, m.counts = self._plan_header()
+        tiles = max(m.tiles_all, ws.min_tiles)
+        if tiles:
+            ws.ensure(tiles)
+            rec = ws.rec()
+            if rec[0] is not pre_rec:                               # (the workspace grew: a new, unfilled buffer)
+                rec[0][: tiles * 32].fill_(-1)
+            if m.tiles_all:
+                self._march_launch("march_fill" + tag, "fill", m, s, *[_lib.ptr(t) for t in rec])
+        return m
 
     def pack(self, which: str, kind: int, weights: List[torch.Tensor], biases: List[torch.Tensor]):
         """Rewrite one net's reference-layout tensors into MFMA operand order.  Inside ``with eng.packing():`` the nets of
@@ -448,18 +569,30 @@ class FineEngine:
     def _H(self, names):
         return _lib.ptr_array([self.ws[n] for n in names])
 
-    def feat_args(self, rays_o, rays_d, viewdirs, sdf, tiles_on, tiles_all, color_on, color_off, ws=None):
-        """esr_feat_args_t for march-record sampling (the tensors must outlive the launches)."""
-        ws = ws or self.ws
+    def feat_args(self, m: March, rec, color_on, color_off):
+        """esr_feat_args_t for sampling at the records ``rec`` (a workspace's four record arrays) of the march ``m``; the
+        tensors must outlive the launches."""
         fa = _lib.EsrFeatArgs()
-        fa.rays_o, fa.rays_d, fa.viewdirs = rays_o.data_ptr(), rays_d.data_ptr(), viewdirs.data_ptr()
-        fa.rec_ray, fa.rec_step, fa.rec_sdf = ws["rec_ray"].data_ptr(), ws["rec_step"].data_ptr(), ws["rec_sdf"].data_ptr()
-        fa.sdf = sdf.data_ptr()
+        fa.rays_o, fa.rays_d, fa.viewdirs = m.rays_o.data_ptr(), m.rays_d.data_ptr(), m.viewdirs.data_ptr()
+        fa.rec_ray, fa.rec_step, fa.rec_sdf = rec[0].data_ptr(), rec[1].data_ptr(), rec[3].data_ptr()
+        fa.sdf = m.sdf.data_ptr()
         for g in range(3):
             fa.color_on[g] = color_on[g].data_ptr() if color_on[g] is not None else None
             fa.color_off[g] = color_off[g].data_ptr() if color_off[g] is not None else None
-        fa.tiles_on, fa.tiles_all = tiles_on, tiles_all
+        fa.tiles_on, fa.tiles_all = m.tiles_on, m.tiles_all
         return fa
+
+    def _tone_wgrad(self, x, dz, t0, t1, gw, gb, amax, s, name):
+        """The tone mapper's weight gradients from Xt and dzt alone: the hidden layer is recomputed inside (tone_wgrad.hip).
+        ``amax`` (f32 engine on the split kernels): products on the 16-bit matrix cores; the gradient operand's scale is this
+        max |dzt| x the net's gain bound, left behind by the split input-gradient kernel (no overflow by construction)."""
+        (w0, w1), (b0, _) = self._raw["tone"]
+        L = self.L
+        fn = L.esr_tone_wgrad_recompute_split if amax is not None else \
+            L.esr_tone_wgrad_recompute_bf16 if self.bf16 else L.esr_tone_wgrad_recompute
+        self._run(name, fn, _lib.ptr(x), _lib.ptr(dz), _lib.ptr(w0.detach()), _lib.ptr(b0.detach()), _lib.ptr(w1.detach()),
+                  *((_lib.ptr(amax),) if amax is not None else ()), t0, t1, _lib.ptr(gw[0]), _lib.ptr(gb[0]), _lib.ptr(gw[1]),
+                  _lib.ptr(gb[1]), _lib.ptr(self.tone_scratch), C.c_int64(self.tone_scratch.numel()), s)
 
     # -- forward -----------------------------------------------------------------
     def forward(self, scene, rays_o, rays_d, viewdirs, em_modes, mask_density, sdf, off_color, emo_color, prelude=None,
@@ -473,11 +606,7 @@ class FineEngine:
 
     def _forward(self, scene, rays_o, rays_d, viewdirs, em_modes, mask_density, sdf, off_color, emo_color, prelude=None):
         """-> (ctx, alphainv_last [N], srgb_marched [N,3], lin_marched [N,3]).
-        sdf [X,Y,Z], off_color/emo_color [X,Y,Z,6], mask_density [mx,my,mz]: contiguous fp32.
-        ``prelude()``: enqueues work that does not depend on the march (weight packing, zeroing the gradient buffer).
-        It is called between the plan kernel and the host's wait for the plan header, on a SIDE stream: the device has
-        work while the host reads the survivor counts and enqueues the rest of the step, and these bandwidth-bound
-        kernels then run beside the march / feature kernels instead of in front of them (tools/trace_step.py)."""
+        sdf [X,Y,Z], off_color/emo_color [X,Y,Z,6], mask_density [mx,my,mz]: contiguous fp32.  ``prelude()``: _march_plan."""
         L, s, ws = self.L, self._s(), self.ws
         n = rays_o.shape[0]
         for t in (rays_o, rays_d, viewdirs):
@@ -485,9 +614,6 @@ class FineEngine:
                 raise RuntimeError("rays must be fp32")
         if em_modes.dtype != torch.int64:
             raise RuntimeError("em_modes must be int64")
-        cached = not self.neus_grad            # one walk per step (esr_fine_march_*_cached); not with neus_alpha "grad"
-        rb = self._ray_buf(n, scene if cached else None)
-        last = torch.empty(n, dtype=torch.float32, device=self.device)
         # everything of the step that starts from zero in ONE fill (each small fill is a ~5 us launch on the step's
         # critical path): plan header (8 x i32; what esr_fine_plan_begin does) | srgb | lin | the loss accumulator
         # every carve starts on a 16-byte boundary (ragged n: a future float4 access must not straddle)
@@ -500,65 +626,15 @@ class FineEngine:
         self._amax_t = zb[8 + 2 * n3 + 2: 8 + 2 * n3 + 3]      # max |dzt| (the tone mapper's)
         sp = C.byref(scene)
         main = torch.cuda.current_stream(self.device)
-        if cached:
-            self._run("march_count", L.esr_fine_march_count_cached, sp, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(mask_density),
-                      _lib.ptr(sdf), n, _lib.ptr(rb["cnt3"]), _lib.ptr(last), _lib.ptr(rb["stats"]), _lib.ptr(plan_dev),
-                      _lib.ptr(rb["cache"]), s)
-        else:
-            self._march("march_count", "count", sp, rays_o, rays_d, viewdirs, _lib.ptr(mask_density),
-                        _lib.ptr(sdf), n, _lib.ptr(rb["cnt3"]), _lib.ptr(last), _lib.ptr(rb["stats"]), _lib.ptr(plan_dev), s)
-        # the counts the host waits for first (a many-workgroup sum), their copy, THEN the one-workgroup scan of the offsets,
-        # which runs while the host reads the header and enqueues
-        self._run("plan_totals", L.esr_fine_plan_totals, _lib.ptr(rb["cnt3"]), _lib.ptr(em_modes), _lib.ptr(rb["stats"]), n,
-                  _lib.ptr(plan_dev), s)
-        self.plan_host.copy_(plan_dev, non_blocking=True)
-        landed = torch.cuda.Event()
-        landed.record()
-        self._run("plan", L.esr_fine_plan_offsets, _lib.ptr(rb["cnt3"]), _lib.ptr(em_modes), n, _lib.ptr(rb["off3"]), _lib.ptr(plan_dev), s)
-        e_pre = None
-        if prelude is not None:
-            # on a side stream: the packing / zeroing kernels are bandwidth-bound and run beside the march and feature
-            # kernels (gather latency) instead of in front of them; the main stream joins before the first MLP launch
-            side = self._side_stream(0)
-            side.wait_event(landed)                                 # (also orders it behind the previous step's readers)
-            with torch.cuda.stream(side):
-                prelude()
-                e_pre = torch.cuda.Event()
-                e_pre.record(side)
-        # padding lanes of the record arrays carry ray -1: filled BEFORE the wait (whole buffer of the previous step's size),
-        # one dispatch less between the read-back and the first kernel that depends on it
-        pre_rec = ws.buf.get("rec_ray")
-        if pre_rec is not None:
-            pre_rec.fill_(-1)
-        landed.synchronize()                                        # the one host wait of the step
-        n_on, n_off, _, _, m0, m1, m2, overflow = [int(v) for v in self.plan_host.tolist()]
-        tiles_on = (n_on + 31) // 32                                # (esr_fine_plan_totals leaves the tile counts to the host)
-        tiles_all = tiles_on + (n_off + 31) // 32
-        if overflow & 1:                                            # (bit 1: the split kernels' range flag, informational)
-            self._overflow()
-        ctx = FineCtx(scene=scene, n_rays=n, tiles_on=tiles_on, tiles_all=tiles_all,
-                      counts=dict(m0=m0, m1=m1, m2=m2, m3=n_on + n_off, n_on=n_on, n_off=n_off),
-                      rays_o=rays_o, rays_d=rays_d, viewdirs=viewdirs, off3=rb["off3"], mask_density=mask_density, sdf=sdf,
-                      f32_only=not self.bf16 and not self.split_fwd)
+        m = self._march_plan(ws, scene, rays_o, rays_d, viewdirs, em_modes, mask_density, sdf, plan_dev=plan_dev, prelude=prelude)
+        last, e_pre, tiles_on, tiles_all = m.last, m.e_pre, m.tiles_on, m.tiles_all
+        ctx = FineCtx(march=m, f32_only=not self.bf16 and not self.split_fwd)
         if tiles_all == 0:
             if e_pre is not None:
                 main.wait_event(e_pre)
             self.range_probe()                                      # (the weight packing may have raised the flag)
             return ctx, last, srgb, lin
-        ws.ensure(tiles_all)
-        if ws["rec_ray"] is not pre_rec:                            # (the workspace grew: a new, unfilled buffer)
-            ws["rec_ray"][: tiles_all * 32].fill_(-1)
-        if cached:
-            self._run("march_fill", L.esr_fine_march_fill_cached, sp, _lib.ptr(rays_o), _lib.ptr(rays_d), n, _lib.ptr(rb["off3"]),
-                      _lib.ptr(rb["stats"]), _lib.ptr(rb["cache"]), _lib.ptr(ws["rec_ray"]), _lib.ptr(ws["rec_step"]),
-                      _lib.ptr(ws["rec_w"]), _lib.ptr(ws["rec_sdf"]), s)
-            ctx.march_cache = (rb["stats"], last, rb["cache"])
-        else:
-            self._march("march_fill", "fill", sp, rays_o, rays_d, viewdirs, _lib.ptr(mask_density),
-                        _lib.ptr(sdf), n, _lib.ptr(rb["off3"]), _lib.ptr(ws["rec_ray"]), _lib.ptr(ws["rec_step"]),
-                        _lib.ptr(ws["rec_w"]), _lib.ptr(ws["rec_sdf"]), s)
-        fa = self.feat_args(rays_o, rays_d, viewdirs, sdf, tiles_on, tiles_all,
-                            color_on=(emo_color, off_color, None), color_off=(off_color, None, None))
+        fa = self.feat_args(m, ws.rec(), color_on=(emo_color, off_color, None), color_off=(off_color, None, None))
         x16 = self.x16 and all(0.0 <= float(r) <= 2.0 for r in scene.grad_feat)
         ctx.x16 = x16
         ctx.amax, ctx.amax_t = self._amax, self._amax_t             # the split weight gradients' scale sources (backward)
@@ -608,62 +684,67 @@ class FineEngine:
         tone-mapped separately, depth, disparity and camera-space normals.  Returns the reference's 12 keys."""
         L, s, ws, dev = self.L, self._s(), self.ws, self.device
         n = rays_o.shape[0]
-        rb = self._ray_buf(n)
-        last = torch.empty(n, dtype=torch.float32, device=dev)
-        sp = C.byref(scene)
         em0 = torch.zeros(n, dtype=torch.int64, device=dev)            # tile partition only: every tile "off"
-        self._run("plan_begin", L.esr_fine_plan_begin, _lib.ptr(self.plan_dev), s)
-        self._march("march_count", "count", sp, rays_o, rays_d, viewdirs, _lib.ptr(mask_density),
-                    _lib.ptr(sdf), n, _lib.ptr(rb["cnt3"]), _lib.ptr(last), _lib.ptr(rb["stats"]), _lib.ptr(self.plan_dev), s)
-        self._run("plan", L.esr_fine_plan, _lib.ptr(rb["cnt3"]), _lib.ptr(em0), _lib.ptr(rb["stats"]), n, _lib.ptr(rb["off3"]),
-                  _lib.ptr(self.plan_dev), s)
-        self.plan_host.copy_(self.plan_dev, non_blocking=True)
-        torch.cuda.current_stream(dev).synchronize()
-        _, _, _, T, m0, m1, m2, overflow = [int(v) for v in self.plan_host.tolist()]
-        if overflow & 1:
-            raise RuntimeError("a ray exceeded scene.max_steps; the LDS bound of the march kernel is wrong")
+        m = self._march_plan(ws, scene, rays_o, rays_d, viewdirs, em0, mask_density, sdf)
+        T = m.tiles_all
         z3 = lambda: torch.zeros(n, 3, dtype=torch.float32, device=dev)
         out = {f"{sp_}/{v}_rgb": z3() for v in ("off", "on", "emo") for sp_ in ("srgb", "lin")}
-        normal_m, depth3 = z3(), z3()
-        depth = torch.zeros(n, dtype=torch.float32, device=dev)
-        disp = torch.empty(n, dtype=torch.float32, device=dev)
         if T:
-            ws.ensure(T)
-            ws["rec_ray"][: T * 32].fill_(-1)
-            self._march("march_fill", "fill", sp, rays_o, rays_d, viewdirs, _lib.ptr(mask_density),
-                        _lib.ptr(sdf), n, _lib.ptr(rb["off3"]), _lib.ptr(ws["rec_ray"]), _lib.ptr(ws["rec_step"]),
-                        _lib.ptr(ws["rec_w"]), _lib.ptr(ws["rec_sdf"]), s)
-            fa = self.feat_args(rays_o, rays_d, viewdirs, sdf, 0, T, color_on=(None, None, None),
-                                color_off=(off_color, emo_color, None))
+            sp = C.byref(scene)
+            fa = self.feat_args(m, ws.rec(), color_on=(None, None, None), color_off=(off_color, emo_color, None))
             self._run("feat_fwd", L.esr_fine_feat_fwd, sp, C.byref(fa), _lib.ptr(ws["X"]), _lib.ptr(ws["gnorm"]), s)
             H, M = self._H(["H0", "H1", "H2"]), self._H(["M0", "M1", "M2"])
             for net, crow, z in (("off", 0, "z_off"), ("emo", 88, "z_emo")):
                 self._run(f"mlp_fwd({net})", self.mlp_fwd, KIND_RADIANCE, _lib.ptr(self.packed[net]), _lib.ptr(ws["X"]), 0, T,
                           H, M, 0, crow, _lib.ptr(ws[z]), s)
-            for name, za, zb, ton in (("off", "z_off", "z_emo", 0), ("emo", "z_emo", "z_emo", 0), ("on", "z_off", "z_emo", T)):
-                self._run("tone_in_fwd", L.esr_fine_tone_in_fwd, _lib.ptr(ws[za]), _lib.ptr(ws[zb]), ton, T,
-                          _lib.ptr(ws["lin"]), _lib.ptr(ws["Xt"]), s)
+
+            def tone():
                 self._run("mlp_fwd(tone)", self.mlp_fwd, KIND_TONEMAP, _lib.ptr(self.packed["tone"]), _lib.ptr(ws["Xt"]), 0, T,
                           self._H(["Ht"]), self._H(["Mt"]), 0, 0, _lib.ptr(ws["zt"]), s)
-                self._run("composite_fwd", L.esr_fine_composite_fwd, _lib.ptr(ws["zt"]), _lib.ptr(ws["lin"]),
-                          _lib.ptr(ws["rec_ray"]), _lib.ptr(ws["rec_w"]), T, _lib.ptr(ws["rgb"]),
-                          _lib.ptr(out[f"srgb/{name}_rgb"]), _lib.ptr(out[f"lin/{name}_rgb"]), s)
-            aux = torch.empty(T * 8 * 32, dtype=torch.float32, device=dev)
-            rt = (C.c_float * 9)(*[float(v) for v in pos_rt.detach().cpu().reshape(-1).tolist()])
-            self._run("eval_aux", L.esr_eval_aux, _lib.ptr(ws["X"]), X_ROWS, 40, 36, 32, _lib.ptr(ws["rec_ray"]),
-                      _lib.ptr(ws["rec_step"]), T, rt, C.c_float(scene.stepdist), _lib.ptr(aux), s)
-            self._run("composite3_fwd(normal)", L.esr_composite3_fwd, _lib.ptr(aux), 8, _lib.ptr(ws["rec_ray"]),
-                      _lib.ptr(ws["rec_w"]), T, _lib.ptr(normal_m), s)
-            self._run("composite3_fwd(depth)", L.esr_composite3_fwd, C.c_void_p(aux.data_ptr() + 4 * 32 * 4), 8,
-                      _lib.ptr(ws["rec_ray"]), _lib.ptr(ws["rec_w"]), T, _lib.ptr(depth3), s)
-        self._run("eval_disp", L.esr_eval_disp, _lib.ptr(depth3), _lib.ptr(last), C.c_float(far), n, _lib.ptr(depth),
-                  _lib.ptr(disp), s)
+                return ws["zt"]
+            self._eval_variants(ws["z_off"], ws["z_emo"], ws["lin"], ws["Xt"], ws["rgb"], ws.rec(), T, tone, out)
+        X, rec = (ws["X"], ws.rec()) if T else (None, None)
+        normal, depth, disp = self._eval_tail(scene, X, X_ROWS, (40, 36, 32), rec, T, pos_rt, far, m.last)
         self.range_probe()
-        out.update({"etc/depth": depth, "etc/disp": disp, "etc/normal": normal_m, "etc/white_bg": last.unsqueeze(-1)})
+        out.update({"etc/depth": depth, "etc/disp": disp, "etc/normal": normal, "etc/white_bg": m.last.unsqueeze(-1)})
         pick = "off" if int(em_mode) == 0 else "on"
         out["srgb/rgb"], out["lin/rgb"] = out[f"srgb/{pick}_rgb"], out[f"lin/{pick}_rgb"]
-        self.last_eval_counts = dict(m0=m0, m1=m1, m2=m2, tiles=T)
+        self.last_eval_counts = dict(m0=m.counts["m0"], m1=m.counts["m1"], m2=m.counts["m2"], tiles=T)
         return out
+
+    def _eval_variants(self, z_off, z_emo, lin, Xt, rgb, rec, T, tone, out):
+        """The off / emo / on radiance variants of an image, each tone-mapped on its own and composited into
+        ``out["srgb/<variant>_rgb"]`` / ``out["lin/<variant>_rgb"]``.  ``tone()``: runs the tone mapper on ``Xt`` and returns
+        its output tile."""
+        s = self._s()
+        for name, za, zb, ton in (("off", z_off, z_emo, 0), ("emo", z_emo, z_emo, 0), ("on", z_off, z_emo, T)):
+            self._run("tone_in_fwd", self.L.esr_fine_tone_in_fwd, _lib.ptr(za), _lib.ptr(zb), ton, T, _lib.ptr(lin), _lib.ptr(Xt), s)
+            zt = tone()
+            self._run("composite_fwd", self.L.esr_fine_composite_fwd, _lib.ptr(zt), _lib.ptr(lin), _lib.ptr(rec[0]),
+                      _lib.ptr(rec[2]), T, _lib.ptr(rgb), _lib.ptr(out[f"srgb/{name}_rgb"]), _lib.ptr(out[f"lin/{name}_rgb"]), s)
+
+    def _eval_tail(self, scene, X, x_rows, cols, rec, T, pos_rt, far, bg, between=None):
+        """The geometry images every ``evaluate`` ends with -> (camera-space normals [N,3], depth [N], disparity [N]).
+        ``X``: the feature tiles, ``x_rows`` rows each, with the unit normal's components at the rows ``cols`` (esr_eval_aux);
+        ``rec``: the march's record arrays over ``T`` tiles; ``bg`` [N]: what the rays leave to the background.
+        ``between()``: launches of the caller's that go in front of the disparity kernel."""
+        L, s, dev = self.L, self._s(), self.device
+        n = bg.shape[0]
+        normal, depth3 = (torch.zeros(n, 3, dtype=torch.float32, device=dev) for _ in range(2))
+        depth = torch.zeros(n, dtype=torch.float32, device=dev)
+        disp = torch.empty(n, dtype=torch.float32, device=dev)
+        if T:
+            aux = torch.empty(T * 8 * 32, dtype=torch.float32, device=dev)
+            rt = (C.c_float * 9)(*[float(v) for v in pos_rt.detach().cpu().reshape(-1).tolist()])
+            self._run("eval_aux", L.esr_eval_aux, _lib.ptr(X), x_rows, *cols, _lib.ptr(rec[0]), _lib.ptr(rec[1]), T, rt,
+                      C.c_float(scene.stepdist), _lib.ptr(aux), s)
+            for name, row0, dst in (("normal", 0, normal), ("depth", 4, depth3)):       # aux rows 0-2: normal colour | row 4: depth
+                self._run(f"composite3_fwd({name})", L.esr_composite3_fwd, C.c_void_p(aux.data_ptr() + row0 * 32 * 4), 8,
+                          _lib.ptr(rec[0]), _lib.ptr(rec[2]), T, _lib.ptr(dst), s)
+            if between is not None:
+                between()
+        self._run("eval_disp", L.esr_eval_disp, _lib.ptr(depth3), _lib.ptr(bg), C.c_float(far), n, _lib.ptr(depth), _lib.ptr(disp), s)
+        return normal, depth, disp
 
     # -- backward ----------------------------------------------------------------
     @_follows_forward
@@ -679,9 +760,9 @@ class FineEngine:
         ``after_grids()`` is called once the grid gradients are complete in stream order: the
         data-parallel step starts the (large) grid all-reduce there, underneath the wgrad kernels.
         A forward that ran on the f32 MFMA kernels (the range fallback) gets an f32 backward."""
-        L, ws = self.L, self.ws
-        sp = C.byref(ctx.scene)
-        to, ta = ctx.tiles_on, ctx.tiles_all
+        L, ws, m = self.L, self.ws, ctx.march
+        sp = C.byref(m.scene)
+        to, ta = m.tiles_on, m.tiles_all
         g_last, g_srgb, g_lin = g_last.contiguous(), g_srgb.contiguous(), g_lin.contiguous()
         main = torch.cuda.current_stream(self.device)
         s = self._s()
@@ -695,24 +776,12 @@ class FineEngine:
         split = not self.bf16 and self.split_fwd
 
         # the march backward's value-tap gradients of the recorded samples ride on the feature backward's SDF window
-        # (ws["dsdf"]) instead of 8 L2 atomics each; not with neus_alpha "grad" (its gradient taps scatter anyway)
+        # (ws["dsdf"]) instead of 8 L2 atomics each; not with neus_alpha "grad" (its gradient taps scatter anyway).  Without
+        # them (no survivor, no SDF gradient asked for) the march backward walks again.
         fold = ta > 0 and not self.neus_grad and grads.get("sdf") is not None
 
         def march_bwd(s_):
-            if fold and ctx.march_cache is not None:
-                st, la, ca = ctx.march_cache
-                self._run("march_bwd", L.esr_fine_march_bwd_cached, sp, _lib.ptr(ctx.rays_o), _lib.ptr(ctx.rays_d), ctx.n_rays,
-                          _lib.ptr(ctx.off3), _lib.ptr(st), _lib.ptr(la), _lib.ptr(ca), _lib.ptr(dweight), _lib.ptr(g_last),
-                          _lib.ptr(grads["sdf"]), _lib.ptr(ws["dsdf"]), 0, s_)
-                return
-            if fold:
-                self._run("march_bwd", L.esr_fine_march_bwd_rec, sp, _lib.ptr(ctx.rays_o), _lib.ptr(ctx.rays_d),
-                          _lib.ptr(ctx.mask_density), _lib.ptr(ctx.sdf), ctx.n_rays, _lib.ptr(ctx.off3), _lib.ptr(dweight),
-                          _lib.ptr(g_last), _lib.ptr(grads["sdf"]), _lib.ptr(ws["dsdf"]), 0, s_)
-                return
-            self._march("march_bwd", "bwd", sp, ctx.rays_o, ctx.rays_d, ctx.viewdirs, _lib.ptr(ctx.mask_density),
-                        _lib.ptr(ctx.sdf), ctx.n_rays, _lib.ptr(ctx.off3), _lib.ptr(dweight), _lib.ptr(g_last),
-                        _lib.ptr(grads["sdf"]), s_)
+            self._march_bwd("march_bwd", m, dweight, g_last, grads["sdf"], ws["dsdf"] if fold else None, 0, s_, walk=not fold)
 
         def feat_bwd(s_):
             src = (_lib.EsrFeatBwdSrc * 1)()
@@ -724,27 +793,11 @@ class FineEngine:
                       _lib.ptr(ws["gnorm"]), src, 1, _lib.ptr(ws["dsdf"]) if fold else None, _lib.ptr(grads["sdf"]),
                       None, None, 0, s_)
 
-        def tone_wgrad(s_):
-            # from Xt and dzt alone: the hidden layer is recomputed inside (tone_wgrad.hip)
-            (w0, w1), (b0, _) = self._raw["tone"]
-            if split:
-                # products on the 16-bit matrix cores; the gradient operand's scale: ctx.amax_t, left behind by the split
-                # input-gradient kernel (max |dzt| x the net's gain bound: no overflow by construction)
-                self._run("tone_wgrad", L.esr_tone_wgrad_recompute_split, _lib.ptr(ws["Xt"]), _lib.ptr(ws["dzt"]), _lib.ptr(w0.detach()),
-                          _lib.ptr(b0.detach()), _lib.ptr(w1.detach()), _lib.ptr(ctx.amax_t), 0, ta, _lib.ptr(grads["tone_w"][0]),
-                          _lib.ptr(grads["tone_b"][0]), _lib.ptr(grads["tone_w"][1]), _lib.ptr(grads["tone_b"][1]),
-                          _lib.ptr(self.tone_scratch), C.c_int64(self.tone_scratch.numel()), s_)
-                return
-            self._run("tone_wgrad", L.esr_tone_wgrad_recompute_bf16 if self.bf16 else L.esr_tone_wgrad_recompute,
-                      _lib.ptr(ws["Xt"]), _lib.ptr(ws["dzt"]), _lib.ptr(w0.detach()),
-                      _lib.ptr(b0.detach()), _lib.ptr(w1.detach()), 0, ta, _lib.ptr(grads["tone_w"][0]),
-                      _lib.ptr(grads["tone_b"][0]), _lib.ptr(grads["tone_w"][1]), _lib.ptr(grads["tone_b"][1]),
-                      _lib.ptr(self.tone_scratch), C.c_int64(self.tone_scratch.numel()), s_)
-
         def wgrads(s_):
             # the tone mapper's by recomputation, then one call for the two radiance nets: layers of the same kernel shape
             # share a launch (esr_mlp_wgrad_batch)
-            tone_wgrad(s_)
+            self._tone_wgrad(ws["Xt"], ws["dzt"], 0, ta, grads["tone_w"], grads["tone_b"], ctx.amax_t if split else None, s_,
+                             "tone_wgrad")
             Hh, dZh = self._H(["H0", "H1", "H2"]), self._H(["dZ0", "dZ1", "dZ2"])
             keep = [Hh, dZh]
             todo = [(KIND_RADIANCE, ws["X"], Hh, dZh, ws["dz"], 0, to, "emo_w", "emo_b"),

@@ -32,7 +32,9 @@ ACT_SOFTPLUS, ACT_SIGMOID = 0, 1
 
 
 class Pass:
-    """Records + tile-major workspace of one sampling pass (grow-only)."""
+    """Records + tile-major workspace of one sampling pass (grow-only, lazy name-keyed buffers).  ``ensure`` / ``rec`` /
+    ``rec_ray_now`` / ``ray_buf`` / ``cache`` / ``min_tiles`` are what ``FineEngine._march_plan`` asks of a workspace."""
+    min_tiles = 1                 # the record arrays exist (one tile of padding) after a march without survivors too
 
     def __init__(self, device, name):
         self.device, self.name = device, name
@@ -43,6 +45,8 @@ class Pass:
         self.n_rays = 0
         self.counts: Dict[str, int] = {}
         self.fa = None            # esr_feat_args_t
+        self.m = None             # fine_engine.March of the pass's last march (the backward reads it)
+        self.cache = None         # its march cache, grow-only
         self.keep: List[torch.Tensor] = []   # tensors referenced by raw pointers
 
     def ensure(self, tiles):
@@ -60,6 +64,18 @@ class Pass:
             self.bufs[name] = t
             self.rows[name] = rows
         return t
+
+    def rec_ray_now(self):
+        return self.bufs.get("rec_ray")
+
+    def rec(self):
+        """The four record arrays of the march (after ``ensure``)."""
+        return (self.buf("rec_ray", 1, torch.int32), self.buf("rec_step", 1, torch.int32), self.buf("rec_w"), self.buf("rec_sdf"))
+
+    def ray_buf(self, n):
+        """Per-ray buffers of a march of ``n`` rays: new ones per march (the step's ctx holds them across the backward)."""
+        i32 = lambda k: torch.empty(k, dtype=torch.int32, device=self.device)
+        return dict(cnt3=i32(n), off3=i32(n), stats=i32(3 * n))
 
     def rowmajor(self, name, tiles=None):
         """[tiles*32, rows] copy of a tile-major buffer."""
@@ -271,119 +287,14 @@ class LtsEngine(FineEngine):
         return v
 
     # ------------------------------------------------------------------ building blocks
-    def _march(self, P: Pass, scene, rays_o, rays_d, em_modes, mask_density, sdf, prelude=None, viewdirs=None, between=None):
-        """count -> plan -> (host reads the plan header) -> fill.  ``viewdirs``: the rays' view directions -- read under cfg
-        neus_alpha "grad" (esrnerf.py:197-200: every march of the renderer extrapolates its section SDFs along them;
-        the secondary rays' view directions are their own directions, esrnerf.py:575-591).  ``prelude()``: work that does not depend on the march
-        (weight packing, zeroing the gradient buffer), enqueued on a side stream while the host waits; the returned
-        event (``P.e_pre``) must be waited for by the main stream before the first consumer.  ``between()``: work for the
-        MAIN stream that does not need the march's result, enqueued behind the plan's copy: the device runs it while the host
-        reads the plan and enqueues the fill (otherwise it idles for the host's wake-up + first launches, ~0.1 ms)."""
-        L, s = self.L, self._s()
-        n = rays_o.shape[0]
-        P.n_rays = n
-        cnt3 = torch.empty(n, dtype=torch.int32, device=self.device)
-        off3 = torch.empty(n, dtype=torch.int32, device=self.device)
-        last = torch.empty(n, dtype=torch.float32, device=self.device)
-        stats = torch.empty(n * 3, dtype=torch.int32, device=self.device)
-        sp = C.byref(scene)
-        self._run("plan_begin", L.esr_fine_plan_begin, _lib.ptr(self.plan_dev), s)
-        ga = self.neus_grad
-        if ga:
-            if viewdirs is None:
-                raise RuntimeError("neus_alpha='grad' marches need the rays' view directions")
-            viewdirs = viewdirs.contiguous()
-            # (no march cache in this mode: the gradient taps are not recorded; fill and backward walk again)
-            self._run(f"march_count[{P.name}]", L.esr_fine_march_count_ga, sp, _lib.ptr(rays_o), _lib.ptr(rays_d),
-                      _lib.ptr(viewdirs), _lib.ptr(mask_density), _lib.ptr(sdf), n, _lib.ptr(cnt3), _lib.ptr(last),
-                      _lib.ptr(stats), _lib.ptr(self.plan_dev), s)
-            P.march = None
-            P.ga = (viewdirs, mask_density, sdf)
-        else:
-            # march cache: the count pass records every mask-cache survivor; fill copies, the backward starts at its scan
-            need = int(L.esr_fine_march_cache_floats(sp, n))
-            if getattr(P, "cache", None) is None or P.cache.numel() < need:
-                P.cache = torch.empty(need, dtype=torch.float32, device=self.device)
-            self._run(f"march_count[{P.name}]", L.esr_fine_march_count_cached, sp, _lib.ptr(rays_o), _lib.ptr(rays_d),
-                      _lib.ptr(mask_density), _lib.ptr(sdf), n, _lib.ptr(cnt3), _lib.ptr(last), _lib.ptr(stats),
-                      _lib.ptr(self.plan_dev), _lib.ptr(P.cache), s)
-            P.march = (stats, last, P.cache)
-        # the counts the host waits for first (a many-workgroup sum), their copy, THEN the one-workgroup scan of the offsets:
-        # it runs while the host reads the header and enqueues (17 / 48 us off the path to the read-back)
-        self._run("plan_totals", L.esr_fine_plan_totals, _lib.ptr(cnt3), _lib.ptr(em_modes), _lib.ptr(stats), n,
-                  _lib.ptr(self.plan_dev), s)
-        self.plan_host.copy_(self.plan_dev, non_blocking=True)
-        P.e_pre = None
-        landed = torch.cuda.Event()
-        landed.record()
-        self._run("plan", L.esr_fine_plan_offsets, _lib.ptr(cnt3), _lib.ptr(em_modes), n, _lib.ptr(off3), _lib.ptr(self.plan_dev), s)
-        if between is not None:
-            between()
-        if prelude is not None:
-            side = self._side_stream(0)
-            side.wait_event(landed)
-            with torch.cuda.stream(side):
-                prelude()
-                P.e_pre = torch.cuda.Event()
-                P.e_pre.record(side)
-        pre_rec = P.bufs.get("rec_ray")       # padding lanes carry ray -1: filled before the wait (fine_engine.forward)
-        if pre_rec is not None:
-            pre_rec.fill_(-1)
-        landed.synchronize()
-        n_on, n_off, _, _, m0, m1, m2, overflow = [int(v) for v in self.plan_host.tolist()]
-        tiles_on = (n_on + 31) // 32                                 # (esr_fine_plan_totals leaves the tile counts to the host)
-        tiles_all = tiles_on + (n_off + 31) // 32
-        if overflow & 1:
-            self._overflow()
-        P.tiles_on, P.tiles_all = tiles_on, tiles_all
-        P.counts = dict(m0=m0, m1=m1, m2=m2, m3=n_on + n_off, n_on=n_on, n_off=n_off)
-        P.ensure(max(tiles_all, 1))
-        rec_ray = P.buf("rec_ray", 1, torch.int32)
-        if rec_ray is not pre_rec:                # (the pass's buffers grew: a new, unfilled one)
-            rec_ray[: max(tiles_all, 1) * 32].fill_(-1)
-        if tiles_all and ga:
-            self._run(f"march_fill[{P.name}]", L.esr_fine_march_fill_ga, sp, _lib.ptr(rays_o), _lib.ptr(rays_d),
-                      _lib.ptr(viewdirs), _lib.ptr(mask_density), _lib.ptr(sdf), n, _lib.ptr(off3), _lib.ptr(rec_ray),
-                      _lib.ptr(P.buf("rec_step", 1, torch.int32)), _lib.ptr(P.buf("rec_w")),
-                      _lib.ptr(P.buf("rec_sdf")), s)
-        elif tiles_all:
-            self._run(f"march_fill[{P.name}]", L.esr_fine_march_fill_cached, sp, _lib.ptr(rays_o), _lib.ptr(rays_d), n,
-                      _lib.ptr(off3), _lib.ptr(stats), _lib.ptr(P.cache), _lib.ptr(rec_ray),
-                      _lib.ptr(P.buf("rec_step", 1, torch.int32)), _lib.ptr(P.buf("rec_w")),
-                      _lib.ptr(P.buf("rec_sdf")), s)
-        P.keep = [rays_o, rays_d, em_modes, cnt3, off3, last, stats]
-        return cnt3, off3, last
-
-    def _march_bwd(self, name, P: Pass, sp, rays_o, rays_d, n, off3, dweight, dlast, grad_sdf, dsdf, acc):
-        """Backward of one march.  Cached form: the value-tap gradients of the recorded samples go to ``dsdf`` (the
-        feature backward folds them into its SDF window).  neus_alpha "grad": a fresh walk that scatters every tap
-        straight into ``grad_sdf`` (``dsdf`` is left untouched).  Returns whether ``dsdf`` was written."""
-        L, s = self.L, self._s()
-        if P.march is None:
-            vd, mask_density, sdf = P.ga
-            self._run(name, L.esr_fine_march_bwd_ga, sp, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(vd),
-                      _lib.ptr(mask_density), _lib.ptr(sdf), n, _lib.ptr(off3), _lib.ptr(dweight), _lib.ptr(dlast),
-                      _lib.ptr(grad_sdf), s)
-            return False
-        st, la, ca = P.march
-        self._run(name, L.esr_fine_march_bwd_cached, sp, _lib.ptr(rays_o), _lib.ptr(rays_d), n, _lib.ptr(off3),
-                  _lib.ptr(st), _lib.ptr(la), _lib.ptr(ca), _lib.ptr(dweight), _lib.ptr(dlast), _lib.ptr(grad_sdf),
-                  _lib.ptr(dsdf) if dsdf is not None else None, acc, s)
-        return dsdf is not None
-
-    def _feat_args_records(self, P: Pass, rays_o, rays_d, viewdirs, sdf, color_on, color_off):
-        fa = _lib.EsrFeatArgs()
-        fa.rays_o, fa.rays_d, fa.viewdirs = rays_o.data_ptr(), rays_d.data_ptr(), viewdirs.data_ptr()
-        fa.rec_ray, fa.rec_step = P.bufs["rec_ray"].data_ptr(), P.bufs["rec_step"].data_ptr()
-        fa.rec_sdf = P.bufs["rec_sdf"].data_ptr()
-        fa.sdf = sdf.data_ptr()
-        for g in range(3):
-            fa.color_on[g] = color_on[g].data_ptr() if color_on[g] is not None else None
-            fa.color_off[g] = color_off[g].data_ptr() if color_off[g] is not None else None
-        fa.tiles_on, fa.tiles_all = P.tiles_on, P.tiles_all
-        P.fa = fa
-        P.keep += [viewdirs]
-        return fa
+    def _march_pass(self, P: Pass, scene, rays_o, rays_d, em_modes, mask_density, sdf, prelude=None, viewdirs=None, between=None):
+        """``_march_plan`` into the records of the pass ``P``, which remembers the march (``P.m``: tile counts, the prelude's
+        event ``P.m.e_pre``, what the backward reads) -> (cnt3, off3, alphainv_last)."""
+        m = P.m = self._march_plan(P, scene, rays_o, rays_d, viewdirs, em_modes, mask_density, sdf, prelude=prelude, between=between,
+                                   tag=f"[{P.name}]")
+        P.n_rays, P.tiles_on, P.tiles_all, P.counts = m.n, m.tiles_on, m.tiles_all, m.counts
+        P.keep = [em_modes]
+        return m.cnt3, m.off3, m.last
 
     def _feat_args_points(self, P: Pass, pts, vd, sdfv, sdf, colors):
         n = pts.shape[0]
@@ -452,21 +363,10 @@ class LtsEngine(FineEngine):
                 self._run(f"mlp_dgrad({net})[{P.name}]", self.mlp_dgrad, kind, _lib.ptr(self.packed[net]),
                           _lib.ptr(dz), t0, t1, _lib.ptr_array(M), _lib.ptr_array([None] * nh if recompute else dZ), _lib.ptr(dX), s)
             if recompute:
-                (w0, w1), (b0, _) = self._raw[net]
-
-                def tone_wgrad(amax_t=amax):
-                    if amax_t is not None:       # (the scale source comes from the split input-gradient kernel)
-                        self._run(f"tone_wgrad[{P.name}]", self.L.esr_tone_wgrad_recompute_split, _lib.ptr(x), _lib.ptr(dz),
-                                  _lib.ptr(w0.detach()), _lib.ptr(b0.detach()), _lib.ptr(w1.detach()), _lib.ptr(amax_t), t0, t1,
-                                  _lib.ptr(gw[0]), _lib.ptr(gb[0]), _lib.ptr(gw[1]), _lib.ptr(gb[1]), _lib.ptr(self.tone_scratch),
-                                  C.c_int64(self.tone_scratch.numel()), self._s())
+                def tone_wgrad(amax_t=amax):           # (the scale source comes from the split input-gradient kernel)
+                    self._tone_wgrad(x, dz, t0, t1, gw, gb, amax_t, self._s(), f"tone_wgrad[{P.name}]")
+                    if amax_t is not None:
                         amax_t.record_stream(torch.cuda.current_stream(self.device))
-                        return
-                    self._run(f"tone_wgrad[{P.name}]",
-                              self.L.esr_tone_wgrad_recompute_bf16 if self.bf16 else self.L.esr_tone_wgrad_recompute, _lib.ptr(x), _lib.ptr(dz),
-                              _lib.ptr(w0.detach()), _lib.ptr(b0.detach()), _lib.ptr(w1.detach()), t0, t1, _lib.ptr(gw[0]),
-                              _lib.ptr(gb[0]), _lib.ptr(gw[1]), _lib.ptr(gb[1]), _lib.ptr(self.tone_scratch),
-                              C.c_int64(self.tone_scratch.numel()), self._s())
                 if self._wgrad_jobs is not None:
                     self._wgrad_extra.append((tone_wgrad, dz))       # with the batched weight gradients, at the end
                 else:
@@ -601,15 +501,13 @@ class LtsEngine(FineEngine):
         n = rays_o.shape[0]
         P0 = self.prim
         self._eval_draws = []                     # the chunks' scattering draws (replayed by the range fallback)
-        cnt3, off3, last = self._march(P0, scene, rays_o, rays_d, torch.zeros(n, dtype=torch.int64, device=dev),
+        cnt3, off3, last = self._march_pass(P0, scene, rays_o, rays_d, torch.zeros(n, dtype=torch.int64, device=dev),
                                        grids["mask"], sdf, viewdirs=viewdirs)
         T, m3 = P0.tiles_all, P0.counts["m3"]
         z3 = lambda: torch.zeros(n, 3, dtype=torch.float32, device=dev)
         out = {f"{sp_}/{v}_rgb": z3() for v in ("off", "on", "emo") for sp_ in ("srgb", "lin")}
-        out.update({"lin/emit": z3(), "lin/basecolor": z3(), "etc/normal": z3()})
-        rm3, depth3 = z3(), z3()
-        depth = torch.zeros(n, dtype=torch.float32, device=dev)
-        disp = torch.empty(n, dtype=torch.float32, device=dev)
+        out.update({"lin/emit": z3(), "lin/basecolor": z3()})
+        rm3 = z3()
         pbr_keys = ("lin/env_dir", "lin/env_indir", "lin/env_effects", "lin/emit_(in)dir", "lin/emit_effects")
         if render_pbr:
             out.update({k: z3() for k in pbr_keys})
@@ -617,24 +515,16 @@ class LtsEngine(FineEngine):
         comp = lambda src, rows, dst, name: self._run(f"composite3_fwd({name})", L.esr_composite3_fwd, src, rows,
                                                       _lib.ptr(P0.bufs["rec_ray"]), _lib.ptr(P0.bufs["rec_w"]), T, _lib.ptr(dst), s)
         if T:
-            self._feat_args_records(P0, rays_o, rays_d, viewdirs, sdf, (offg, emog, brdfg), (offg, emog, brdfg))
+            P0.fa = self.feat_args(P0.m, P0.rec(), (offg, emog, brdfg), (offg, emog, brdfg))
             self._features(P0, scene)
             self._net_fwd(P0, "off", KIND_RADIANCE, 0, 0, T, save=False)
             self._net_fwd(P0, "emo", KIND_RADIANCE, 88, 0, T, save=False)
             self._net_fwd(P0, "brdf", KIND_BRDF, 96, 0, T, save=False)
-            for name, za, zb, ton in (("off", "off.z", "emo.z", 0), ("emo", "emo.z", "emo.z", 0), ("on", "off.z", "emo.z", T)):
-                self._run("tone_in_fwd", L.esr_fine_tone_in_fwd, _lib.ptr(P0.bufs[za]), _lib.ptr(P0.bufs[zb]), ton, T,
-                          _lib.ptr(P0.buf("lin", 4)), _lib.ptr(P0.buf("Xt", XT_ROWS)), s)
-                self._net_fwd(P0, "tone", KIND_TONEMAP, 0, 0, T, save=False)
-                self._run("composite_fwd", L.esr_fine_composite_fwd, _lib.ptr(P0.bufs["tone.z"]), _lib.ptr(P0.bufs["lin"]),
-                          _lib.ptr(P0.bufs["rec_ray"]), _lib.ptr(P0.bufs["rec_w"]), T, _lib.ptr(P0.buf("rgb", 4)),
-                          _lib.ptr(out[f"srgb/{name}_rgb"]), _lib.ptr(out[f"lin/{name}_rgb"]), s)
-            aux = torch.empty(T * 8 * 32, dtype=torch.float32, device=dev)
-            rt = (C.c_float * 9)(*[float(v) for v in pos_rt.detach().cpu().reshape(-1).tolist()])
-            self._run("eval_aux", L.esr_eval_aux, _lib.ptr(P0.bufs["X"]), X_ROWS, 40, 36, 32, _lib.ptr(P0.bufs["rec_ray"]),
-                      _lib.ptr(P0.bufs["rec_step"]), T, rt, C.c_float(scene.stepdist), _lib.ptr(aux), s)
-            comp(_lib.ptr(aux), 8, out["etc/normal"], "normal")
-            comp(C.c_void_p(aux.data_ptr() + 4 * 32 * 4), 8, depth3, "depth")
+            tone = lambda: self._net_fwd(P0, "tone", KIND_TONEMAP, 0, 0, T, save=False)
+            self._eval_variants(P0.bufs["off.z"], P0.bufs["emo.z"], P0.buf("lin", 4), P0.buf("Xt", XT_ROWS), P0.buf("rgb", 4),
+                                P0.rec(), T, tone, out)
+
+        def heads():
             # material heads; the emission head reads emit_color, which may be a frozen copy distinct from emo_color
             self._act(P0, "brdf.z", "brdf.a", 8, 5, ACT_SIGMOID)
             comp(_lib.ptr(P0.bufs["brdf.a"]), 8, out["lin/basecolor"], "basecolor")
@@ -644,15 +534,15 @@ class LtsEngine(FineEngine):
             else:
                 keep_x, keep_g = P0.bufs["X"], P0.bufs["gnorm"]
                 P0.bufs["X"], P0.bufs["gnorm"] = P0.buf("X.emit", X_ROWS), P0.buf("gnorm.emit", 4)
-                self._feat_args_records(P0, rays_o, rays_d, viewdirs, sdf, (emitg, None, None), (emitg, None, None))
+                P0.fa = self.feat_args(P0.m, P0.rec(), (emitg, None, None), (emitg, None, None))
                 self._features(P0, scene)
                 self._net_fwd(P0, "emit", KIND_EMIT, 0, 0, T, save=False)
                 P0.bufs["X"], P0.bufs["gnorm"] = keep_x, keep_g
             self._act(P0, "emit.z", "emit.a", 4, 3, ACT_SOFTPLUS)
             comp(_lib.ptr(P0.bufs["emit.a"]), 4, out["lin/emit"], "emit")
-        self._run("eval_disp", L.esr_eval_disp, _lib.ptr(depth3), _lib.ptr(last), C.c_float(far), n, _lib.ptr(depth),
-                  _lib.ptr(disp), s)
-        out.update({"etc/depth": depth, "etc/disp": disp, "etc/white_bg": last.unsqueeze(-1),
+        normal, depth, disp = self._eval_tail(scene, P0.bufs.get("X"), X_ROWS, (40, 36, 32), P0.rec(), T, pos_rt, far, last,
+                                              between=heads)
+        out.update({"etc/normal": normal, "etc/depth": depth, "etc/disp": disp, "etc/white_bg": last.unsqueeze(-1),
                     "lin/roughness": rm3[:, 0].contiguous(), "lin/metallic": rm3[:, 1].contiguous()})
         if render_pbr and T:
             R = int(num_2ndrays)
@@ -682,12 +572,12 @@ class LtsEngine(FineEngine):
                 self._run("lts_dirs", L.esr_lts_dirs, _lib.ptr(raw1), _lib.ptr(normal_c), nc, R + 1, _lib.ptr(dirs_all), s)
                 o2 = pts_c.repeat_interleave(R, 0).contiguous()
                 d2 = dirs_all[:, :R].reshape(nc * R, 3).contiguous()
-                _, _, last2 = self._march(P2, scene2, o2, d2, torch.zeros(nc * R, dtype=torch.int64, device=dev),
+                _, _, last2 = self._march_pass(P2, scene2, o2, d2, torch.zeros(nc * R, dtype=torch.int64, device=dev),
                                           grids["mask"], sdf, viewdirs=d2)
                 T2 = P2.tiles_all
                 off_m, emo_m = torch.zeros(nc * R, 3, device=dev), torch.zeros(nc * R, 3, device=dev)
                 if T2:
-                    self._feat_args_records(P2, o2, d2, d2, sdf, (offg, emog, None), (offg, emog, None))
+                    P2.fa = self.feat_args(P2.m, P2.rec(), (offg, emog, None), (offg, emog, None))
                     self._features(P2, scene2)
                     self._net_fwd(P2, "off", KIND_RADIANCE, 0, 0, T2, save=False)
                     self._net_fwd(P2, "emo", KIND_RADIANCE, 88, 0, T2, save=False)
@@ -734,7 +624,7 @@ class LtsEngine(FineEngine):
         L, s, dev = self.L, self._s(), self.device
         n = rays_o.shape[0]
         P0 = self.prim
-        self._march(P0, scene, rays_o, rays_d, torch.zeros(n, dtype=torch.int64, device=dev), mask_density, sdf,
+        self._march_pass(P0, scene, rays_o, rays_d, torch.zeros(n, dtype=torch.int64, device=dev), mask_density, sdf,
                     viewdirs=viewdirs)
         T = P0.tiles_all
         out = torch.zeros(n, 3, dtype=torch.float32, device=dev)
@@ -742,7 +632,7 @@ class LtsEngine(FineEngine):
             return out
         sp = C.byref(scene)
         if what == "emit":
-            self._feat_args_records(P0, rays_o, rays_d, viewdirs, sdf, (emit_grid, None, None), (emit_grid, None, None))
+            P0.fa = self.feat_args(P0.m, P0.rec(), (emit_grid, None, None), (emit_grid, None, None))
             self._features(P0, scene)
             self._net_fwd(P0, "emit", KIND_EMIT, 0, 0, T, save=False)
             v = self._act(P0, "emit.z", "emit.a", 4, 3, ACT_SOFTPLUS)
@@ -781,7 +671,7 @@ class LtsEngine(FineEngine):
         rays_o, rays_d, viewdirs = batch["rays_o"], batch["rays_d"], batch["viewdirs"]
         N = rays_o.shape[0]
         P0, P1, P2 = self.prim, self.pts, self.sec
-        cnt3, off3, _ = self._march(P0, scene, rays_o, rays_d, torch.zeros(N, dtype=torch.int64, device=dev),
+        cnt3, off3, _ = self._march_pass(P0, scene, rays_o, rays_d, torch.zeros(N, dtype=torch.int64, device=dev),
                                     grids["mask"], sdf, viewdirs=viewdirs)
         T, m3 = P0.tiles_all, P0.counts["m3"]
         if T == 0:
@@ -831,12 +721,12 @@ class LtsEngine(FineEngine):
         # incoming emo radiance along the secondary rays (no gradient: esrnerf.py:241 no_grad)
         o2 = pts_p.repeat_interleave(R, 0).contiguous()
         d2 = dirs_all[:, :R].reshape(Pn * R, 3).contiguous()
-        _, _, last2 = self._march(P2, scene2, o2, d2, torch.zeros(Pn * R, dtype=torch.int64, device=dev), grids["mask"], sdf,
+        _, _, last2 = self._march_pass(P2, scene2, o2, d2, torch.zeros(Pn * R, dtype=torch.int64, device=dev), grids["mask"], sdf,
                                   viewdirs=d2)
         T2 = P2.tiles_all
         emo_m = torch.zeros(Pn * R, 3, device=dev)
         if T2:
-            self._feat_args_records(P2, o2, d2, d2, sdf, (None, emog, None), (None, emog, None))
+            P2.fa = self.feat_args(P2.m, P2.rec(), (None, emog, None), (None, emog, None))
             self._features(P2, scene2)
             self._net_fwd(P2, "emo", KIND_RADIANCE, 88, 0, T2, save=False)
             self._act(P2, "emo.z", "emo.a", 4, 3, ACT_SOFTPLUS)
@@ -886,7 +776,7 @@ class LtsEngine(FineEngine):
         rays_o, rays_d, viewdirs = batch["rays_o"], batch["rays_d"], batch["viewdirs"]
         N = rays_o.shape[0]
         P0 = self.prim
-        cnt3, off3, last = self._march(P0, scene, rays_o, rays_d, batch["em_modes"], grids["mask"], sdf, prelude=prelude,
+        cnt3, off3, last = self._march_pass(P0, scene, rays_o, rays_d, batch["em_modes"], grids["mask"], sdf, prelude=prelude,
                                        viewdirs=viewdirs)
         T, Ton = P0.tiles_all, P0.tiles_on
         srgb = self._z(N, 3, device=dev)
@@ -901,7 +791,7 @@ class LtsEngine(FineEngine):
         if T == 0:
             raise RuntimeError("LTS step with no surviving sample (degenerate batch)")
         sp = C.byref(scene)
-        self._feat_args_records(P0, rays_o, rays_d, viewdirs, sdf, (offg, emog, brdfg), (offg, emog, brdfg))
+        P0.fa = self.feat_args(P0.m, P0.rec(), (offg, emog, brdfg), (offg, emog, brdfg))
         self._features(P0, scene)
         # (handing the draw to the library's worker thread is ~7 us of host time; the draw itself is 0.2-0.4 ms against
         # ~0.6 ms of primary-pass work queued in front of its consumer)
@@ -913,8 +803,8 @@ class LtsEngine(FineEngine):
         pts_all = torch.empty(T * 32, 3, device=dev)
         self._run("sample_points", L.esr_sample_points, sp, _lib.ptr(rays_o), _lib.ptr(rays_d),
                   _lib.ptr(P0.bufs["rec_ray"]), _lib.ptr(P0.bufs["rec_step"]), T * 32, _lib.ptr(pts_all), s)
-        if P0.e_pre is not None:                  # packed weights (and the zeroed gradient buffer) from the side stream
-            torch.cuda.current_stream(dev).wait_event(P0.e_pre)
+        if P0.m.e_pre is not None:                  # packed weights (and the zeroed gradient buffer) from the side stream
+            torch.cuda.current_stream(dev).wait_event(P0.m.e_pre)
         # radiance heads: off on every tile, emo on the on-tiles (both carry gradients, esrnerf.py:751-757)
         self._net_fwd(P0, "off", KIND_RADIANCE, 0, 0, T)
         self._net_fwd(P0, "emo", KIND_RADIANCE, 88, 0, Ton)
@@ -1047,13 +937,13 @@ class LtsEngine(FineEngine):
         # works on it while the host waits for the plan header and enqueues the fill
         P2 = self.sec
         em2 = self._z(Pn * R, dtype=torch.int64, device=dev)
-        _, off3_2, last2 = self._march(P2, scene2, o2, d2, em2, grids["mask"], sdf, viewdirs=d2, between=points_pass)
+        _, off3_2, last2 = self._march_pass(P2, scene2, o2, d2, em2, grids["mask"], sdf, viewdirs=d2, between=points_pass)
         off_pt, emo_pt = at_pts["off"], at_pts["emo"]
         T2 = P2.tiles_all
         off_m = self._z(Pn * R, 3, device=dev)
         emo_m = self._z(Pn * R, 3, device=dev)
         if T2:
-            self._feat_args_records(P2, o2, d2, d2, sdf, (offg, emog, None), (offg, emog, None))
+            P2.fa = self.feat_args(P2.m, P2.rec(), (offg, emog, None), (offg, emog, None))
             self._features(P2, scene2)
             self._net_fwd(P2, "off", KIND_RADIANCE, 0, 0, T2)
             self._net_fwd(P2, "emo", KIND_RADIANCE, 88, 0, T2)
@@ -1199,7 +1089,7 @@ class LtsEngine(FineEngine):
         Pn, R = ctx.n_pts, ctx.n_2nd
         perm, jp = ctx.perm, ctx.jp
         zero = lambda k, shape: g[k].contiguous() if g.get(k) is not None else self._z(shape, device=dev)
-        sp, sp2 = C.byref(ctx.scene), C.byref(ctx.scene2)
+        sp = C.byref(ctx.scene)
         b = ctx.batch
         grid_g = grads
 
@@ -1235,15 +1125,13 @@ class LtsEngine(FineEngine):
             ds2 = P2.buf("dsdf")
 
             def scatter2():
-                wrote = self._march_bwd("march_bwd[secondary]", P2, sp2, ctx.t["o2"], ctx.t["d2"], Pn * R, ctx.t["off3_2"], dw2,
-                                        d["d_last2"], grads["sdf"], ds2, 0)
+                wrote = self._march_bwd("march_bwd[secondary]", P2.m, dw2, d["d_last2"], grads["sdf"], ds2, 0, self._s())
                 self._feat_bwd(P2, ctx.scene2, src, grads["sdf"], dsdf_extra=ds2 if wrote else None)
             # the secondary pass's grid scatters (incoherent rays: L2 atomics, ~0.4 ms with the matrix cores idle) on a stream of
             # their own, beside the input-gradient chains of the points' and the primary pass that follow on the main stream
             self._on_scatter_stream(1, scatter2)
         else:
-            self._march_bwd("march_bwd[secondary]", P2, sp2, ctx.t["o2"], ctx.t["d2"], Pn * R, ctx.t["off3_2"], z(32),
-                            d["d_last2"], grads["sdf"], None, 0)
+            self._march_bwd("march_bwd[secondary]", P2.m, z(32), d["d_last2"], grads["sdf"], None, 0, s)
 
         # ---- radiance at the points
         T1 = P1.tiles_all
@@ -1304,8 +1192,7 @@ class LtsEngine(FineEngine):
             g4n[perm, 1:4] = g["etc/normal"]
 
         def scatter0(src=src):
-            self._march_bwd("march_bwd", P0, sp, b["rays_o"], b["rays_d"], P0.n_rays, ctx.t["off3"], dweight, g_last,
-                            grads["sdf"], dsdf_extra, 1)
+            self._march_bwd("march_bwd", P0.m, dweight, g_last, grads["sdf"], dsdf_extra, 1, self._s())
             self._feat_bwd(P0, ctx.scene, src, grads["sdf"], dsdf_extra=dsdf_extra, grad4=g4n)
         # (beside the perturbed heads' chain below, which does not depend on them)
         self._on_scatter_stream(2, scatter0)

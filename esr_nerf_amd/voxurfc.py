@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, render_utils
-from .fine_engine import DX_ROWS, FineEngine, make_scene
+from .fine_engine import DX_ROWS, FineEngine, _Workspace, make_scene
 from .modules import DenseGrid, ForwardSwitch, Gaussian3DConv, GradientConv, MaskCache, _linears, _mlp_stack
 
 KIND_COARSE = 4
@@ -34,30 +34,18 @@ class CoarseEngine(FineEngine):
         for k in ("off", "emo"):
             self.packed[k] = torch.empty(self.L.esr_mlp_packed_floats(KIND_COARSE), dtype=torch.float32,
                                          device=self.device)
-        self.cap = 0
-        self.b: Dict[str, torch.Tensor] = {}
+        self.ws = _Workspace(self.device, self.ROWS, self.OTHER)
 
     ROWS = dict(X=XC_ROWS, gnorm=1, rec_w=1, rec_sdf=1, rgb=4, dweight=1,
                 **{f"{n}.{k}": r for n in ("off", "emo") for k, r in
                    (("H0", HID), ("H1", HID), ("z", 4), ("dz", 4), ("dZ0", HID), ("dZ1", HID), ("dX", DX_ROWS))})
-
-    def _ensure(self, tiles):
-        if tiles <= self.cap:
-            return
-        cap = max(tiles, int(self.cap * 1.25) + 16)
-        dev = self.device
-        self.b = {k: torch.empty(cap * r * 32, dtype=torch.float32, device=dev) for k, r in self.ROWS.items()}
-        for n in ("off", "emo"):
-            for l in (0, 1):
-                self.b[f"{n}.M{l}"] = torch.empty(cap * 4 * 32, dtype=torch.int32, device=dev)
-        self.b["rec_ray"] = torch.empty(cap * 32, dtype=torch.int32, device=dev)
-        self.b["rec_step"] = torch.empty(cap * 32, dtype=torch.int32, device=dev)
-        self.cap = cap
+    OTHER = dict(rec_ray=(32, torch.int32), rec_step=(32, torch.int32),
+                 **{f"{n}.M{l}": (4 * 32, torch.int32) for n in ("off", "emo") for l in (0, 1)})
 
     def forward(self, scene, batch, sdf, kernel_w, ksize, voxel_size, mask_density, off_color, emo_color):
         """sdf [X,Y,Z]; off/emo_color [X,Y,Z,12]; kernel_w: ctypes float array (k^3, host).
         -> (ctx, alphainv_last [N], white_bg [N,1], srgb [N,3])"""
-        L, s, dev, b = self.L, self._s(), self.device, self.b
+        L, s, dev = self.L, self._s(), self.device
         rays_o, rays_d, viewdirs, em_modes = batch["rays_o"], batch["rays_d"], batch["viewdirs"], batch["em_modes"]
         n = rays_o.shape[0]
         dims = [int(v) for v in sdf.shape]
@@ -86,17 +74,14 @@ class CoarseEngine(FineEngine):
                   _lib.ptr(self.plan_dev), s)
         self.plan_host.copy_(self.plan_dev, non_blocking=True)
         torch.cuda.current_stream(dev).synchronize()
-        n_on, n_off, tiles_on, tiles_all, m0, m1, m2, overflow = [int(v) for v in self.plan_host.tolist()]
-        if overflow & 1:                                   # (bit 1: the fine stage's split-fp16 range flag, not this renderer's)
-            raise RuntimeError("a ray exceeded scene.max_steps; the LDS bound of the march kernel is wrong")
+        tiles_on, tiles_all, counts = self._plan_header()
         ctx = dict(scene=scene, batch=batch, n=n, T=tiles_all, Ton=tiles_on, sm=sm, gg=gg, off3=off3, dims=dims,
-                   mask_density=mask_density, kernel_w=kernel_w, ksize=ksize, voxel=voxel_size,
-                   counts=dict(m0=m0, m1=m1, m2=m2, m3=n_on + n_off, n_on=n_on, n_off=n_off))
+                   mask_density=mask_density, kernel_w=kernel_w, ksize=ksize, voxel=voxel_size, counts=counts)
         white_bg = (1.0 - cumw).unsqueeze(-1)
         if tiles_all == 0:
             return ctx, last, white_bg, srgb
-        self._ensure(tiles_all)
-        b = self.b
+        self.ws.ensure(tiles_all)
+        b = self.ws
         T, Ton = tiles_all, tiles_on
         b["rec_ray"][: T * 32].fill_(-1)
         if self.neus_grad:
@@ -129,28 +114,17 @@ class CoarseEngine(FineEngine):
                      em_modes=torch.ones(n, dtype=torch.int64, device=dev))          # every tile carries both colour groups
         ctx, _, white_bg, _ = self.forward(scene, batch, sdf, kernel_w, ksize, voxel_size, mask_density, off_color,
                                            emo_color)
-        T, b = ctx["T"], self.b
+        T, b = ctx["T"], self.ws
         z3 = lambda: torch.zeros(n, 3, dtype=torch.float32, device=dev)
         out = {"srgb/off_rgb": z3(), "srgb/emo_rgb": z3()}
-        normal_m, depth3 = z3(), z3()
-        depth, disp = torch.zeros(n, device=dev), torch.empty(n, device=dev)
         if T:
             act = torch.empty(T * 4 * 32, dtype=torch.float32, device=dev)
             for net in ("off", "emo"):
                 self._run("act_fwd", L.esr_act_fwd, _lib.ptr(b[f"{net}.z"]), T, 4, 3, 1, _lib.ptr(act), s)
                 self._run(f"composite3_fwd({net})", L.esr_composite3_fwd, _lib.ptr(act), 4, _lib.ptr(b["rec_ray"]),
                           _lib.ptr(b["rec_w"]), T, _lib.ptr(out[f"srgb/{net}_rgb"]), s)
-            aux = torch.empty(T * 8 * 32, dtype=torch.float32, device=dev)
-            rt = (C.c_float * 9)(*[float(v) for v in pos_rt.detach().cpu().reshape(-1).tolist()])
-            self._run("eval_aux", L.esr_eval_aux, _lib.ptr(b["X"]), XC_ROWS, 24, 25, 26, _lib.ptr(b["rec_ray"]),
-                      _lib.ptr(b["rec_step"]), T, rt, C.c_float(scene.stepdist), _lib.ptr(aux), s)
-            self._run("composite3_fwd(normal)", L.esr_composite3_fwd, _lib.ptr(aux), 8, _lib.ptr(b["rec_ray"]),
-                      _lib.ptr(b["rec_w"]), T, _lib.ptr(normal_m), s)
-            self._run("composite3_fwd(depth)", L.esr_composite3_fwd, C.c_void_p(aux.data_ptr() + 4 * 32 * 4), 8,
-                      _lib.ptr(b["rec_ray"]), _lib.ptr(b["rec_w"]), T, _lib.ptr(depth3), s)
-        bg = white_bg.reshape(-1).contiguous()
-        self._run("eval_disp", L.esr_eval_disp, _lib.ptr(depth3), _lib.ptr(bg), C.c_float(far), n, _lib.ptr(depth),
-                  _lib.ptr(disp), s)
+        X, rec = (b["X"], b.rec()) if T else (None, None)
+        normal_m, depth, disp = self._eval_tail(scene, X, XC_ROWS, (24, 25, 26), rec, T, pos_rt, far, white_bg.reshape(-1).contiguous())
         out["srgb/on_rgb"] = out["srgb/off_rgb"] + out["srgb/emo_rgb"]          # segment sums are linear
         out.update({"etc/depth": depth, "etc/disp": disp, "etc/normal": normal_m, "etc/white_bg": white_bg})
         out["srgb/rgb"] = out["srgb/off_rgb"] if int(em_mode) == 0 else out["srgb/on_rgb"]
@@ -158,7 +132,7 @@ class CoarseEngine(FineEngine):
 
     def backward(self, ctx, g_last, g_wbg, g_srgb, grads):
         """grads (zero-initialised): sdf [X,Y,Z], off_color / emo_color [X,Y,Z,12], off_w/off_b/emo_w/emo_b (3 each)."""
-        L, s, dev, b = self.L, self._s(), self.device, self.b
+        L, s, dev, b = self.L, self._s(), self.device, self.ws
         T, Ton, n, dims = ctx["T"], ctx["Ton"], ctx["n"], ctx["dims"]
         sp = C.byref(ctx["scene"])
         bt = ctx["batch"]

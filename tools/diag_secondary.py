@@ -43,15 +43,15 @@ print("surface points per tile: hist", np.bincount(ppt)[:6])
 # ---- where the survivors of one surface point's 256 rays lie, relative to the point (what a per-point accumulation window in
 # feat_bwd could catch): cells from the ray origin + direction * (near + step * stepdist)
 cap = {}
-orig_march = eng._march
+orig_march = eng._march_pass
 def spy(P, scene_, o, d, *a, **k):
     if P is eng.sec:
         cap["o"], cap["d"], cap["near"], cap["stepdist"] = o.detach().clone(), d.detach().clone(), float(scene_.near_), float(scene_.stepdist)
     return orig_march(P, scene_, o, d, *a, **k)
-eng._march = spy
+eng._march_pass = spy
 step.forward_loss_backward(batch, 220.0)
 torch.cuda.synchronize()
-eng._march = orig_march
+eng._march_pass = orig_march
 rr = P2.bufs["rec_ray"].cpu().numpy(); rs = P2.bufs["rec_step"].cpu().numpy()
 ok = rr >= 0
 o, d = cap["o"].cpu().numpy(), cap["d"].cpu().numpy()
