@@ -160,7 +160,16 @@ EXPORTS = [
     "esr_cd_nn",
     "esr_dvgo_fwd", "esr_dvgo_eval", "esr_dvgo_bwd", "esr_dvgo_count", "esr_dvgo_count_add",
     "esr_ssim", "esr_view_post", "esr_sqerr_sum", "esr_gamma_curve", "esr_mask_iou",
+    "esr_mask_dilate", "esr_edit_label",
 ]
+
+# full ctypes signatures (argument conversion checked on every call) of the entries that declare them
+SIGNATURES = {
+    "esr_mask_dilate": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "esr_edit_label": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]),
+}
 
 
 def lib() -> C.CDLL:
@@ -196,6 +205,9 @@ def lib() -> C.CDLL:
                      "esr_mask_iou"):
             if hasattr(L, name):
                 getattr(L, name).restype = C.c_int
+        for name, (res, args) in SIGNATURES.items():
+            if hasattr(L, name):
+                getattr(L, name).restype, getattr(L, name).argtypes = res, args
         if L.esr_abi_version() != ABI_VERSION:
             raise RuntimeError("libesr_hip.so ABI version mismatch: rebuild")
         _lib = L

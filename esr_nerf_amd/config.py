@@ -66,6 +66,11 @@ LTS_TRAINER = dict(weight_entropy_last=0.001, weight_tv_density=0.01, weight_lin
 PDRA_TRAINER = dict(LTS_TRAINER, weight_emit_smooth=0.1, weight_lts_l=50.0, weight_lts_r=1.0, weight_emit_supp=0.1)
 
 
+# cfg/app/pdra.yaml:117-138, the keys the re-lighting fine-tune reads (esr_nerf_amd/relight.py)
+PDRA_EVAL = dict(batch_size=8192, uncert_batch_size=4096, cert_batch_size=4096, n_iters=20000, mask_dilation_ks=10,
+                 lrs=dict(emo_color=0.001, emo_rgbnet=1e-05), weight_lts=0.5)
+
+
 # /root/reference/cfg/app/coarse.yaml:12-32 (model), :75-77 (loss weights)
 COARSE_MODEL = dict(mask_ks=3, maskcache_thres=0.001, fastcolor_thres=0.0001, stepsize=0.5, num_voxels=884736,
                     color_dim=12, rgbnet_width=128, rgbnet_depth=3, posbase_pe=5, viewbase_pe=1, smooth_ksize=5,
@@ -104,7 +109,8 @@ def lts_cfg(device: str = "cpu", **model_over) -> AttrDict:
     m.update(model_over)
     return AttrDict(
         system=dict(device=device, debug=True, seed=0, tqdm_iters=10),
-        app=dict(model=m, trainer=dict(PDRA_TRAINER)),      # superset of the lts keys
+        app=dict(model=m, trainer=dict(PDRA_TRAINER),       # superset of the lts keys
+                 eval=dict(PDRA_EVAL, lrs=dict(PDRA_EVAL["lrs"]))),
         data=dict(white_bg=True),
         global_step=0,
     )

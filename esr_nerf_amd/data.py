@@ -136,6 +136,15 @@ class RayGroupManager:
         self.cert_data_idxs = torch.cat([self.cert_data_idxs, self.uncert_data_idxs[~mask]]).contiguous()
         self.uncert_data_idxs = self.uncert_data_idxs[mask].contiguous()
 
+    def set_rows(self, key: str, rows: torch.Tensor, values: torch.Tensor, fill=0):
+        """``data[key]`` becomes a NEW full-length array: ``values`` at the original rows ``rows``, ``fill`` elsewhere -- what
+        the reference's ``uncert_data[key] = values; cert_data[key] = fill`` (pdra.py:1030-1042) means for arrays that stay
+        at their original rows.  The array it replaces (which may be the dataset's own) is not written."""
+        n = len(self.data[self.keys[0]])
+        full = torch.full((n, *values.shape[1:]), fill, dtype=values.dtype, device=self.home)
+        full[rows.to(self.home)] = values.to(self.home)
+        self.data[key] = _pin(full) if self.data_preload_to_cpu else full
+
     def uncert(self, key: str) -> torch.Tensor:
         return self.data[key][self.uncert_data_idxs]
 

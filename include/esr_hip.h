@@ -1228,6 +1228,33 @@ int esr_gamma_curve(const float *x, int64_t n, float *y, void *stream);
 /* IoU counts -- replaces utils2/metric.py:95-98.  mask1, mask2 [n] u8 / bool; counts [2] i64 = |m1 & m2|, |m1 | m2| */
 int esr_mask_iou(const uint8_t *mask1, const uint8_t *mask2, int64_t n, int64_t *counts, void *stream);
 
+/* ------------------------------------------------------------------------- *
+ * K. Re-lighting edit rays (app/fine/pdra.py:934-1045, filter_edit_rays)
+ * ------------------------------------------------------------------------- */
+
+#define ESR_RELIGHT_MAX_COND 16  /* most edit conditions of a view (ESR_ECAP beyond it: they travel as kernel arguments) */
+
+/*
+ * Grey-level dilation of masks [n_cond,h,w] f32 by a ks x ks box into out (same shape, not masks itself) -- replaces
+ * cv2.dilate(src, np.ones((ks, ks)), iterations=1) of pdra.py:945-962: anchor ks / 2, i.e. the window
+ * dy, dx in [-(ks / 2), ks - 1 - ks / 2] (NOT symmetric for an even ks), pixels outside the image take no part.  Any
+ * ks >= 1, h, w >= 1; a window that is larger than the image is clipped to it.  ESR_ECAP when the clipped tile plus halo
+ * does not fit a CU's LDS (windows beyond ~130 pixels on images that large).  Bit-identical to the definition.
+ */
+int esr_mask_dilate(const float *masks, int32_t n_cond, int32_t h, int32_t w, int32_t ks, float *out, void *stream);
+/*
+ * Edit labels of n rays from their expected surface points esp [n,3] f32 -- replaces pdra.py:988-1028.  w2c [host] f32
+ * [16]: the inverse of the view's pose, row-major; focal, w, h: the camera (K = [[-f,0,w/2-0.5],[0,f,h/2-0.5],[0,0,1]]);
+ * masks [n_cond,h,w] f32: the DILATED masks; cond_modes [host] i64 [n_cond] (0..4, else ESR_EINVAL), cond_intensities
+ * [host] f32 [n_cond] and cond_colors [host] f32 [n_cond,2] (NULL = zeros).  Outputs: keep u8 [n] (some condition
+ * matched), em_modes i64 [n], em_colors f32 [n,2], em_intensities f32 [n] as esr_emit_edit takes them; uv (or NULL) f32
+ * [n,2]: the projected pixel coordinates (diagnostics).  One launch, no atomics: the same bytes on every call.
+ * Arithmetic, the reference quirks that are reproduced and the non-finite case: the header of csrc/relight.hip.
+ */
+int esr_edit_label(const float *esp, int64_t n, const float *w2c, float focal, int32_t w, int32_t h, const float *masks,
+                   int32_t n_cond, const int64_t *cond_modes, const float *cond_intensities, const float *cond_colors,
+                   uint8_t *keep, int64_t *em_modes, float *em_colors, float *em_intensities, float *uv, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
