@@ -161,6 +161,7 @@ EXPORTS = [
     "esr_dvgo_fwd", "esr_dvgo_eval", "esr_dvgo_bwd", "esr_dvgo_count", "esr_dvgo_count_add",
     "esr_ssim", "esr_view_post", "esr_sqerr_sum", "esr_gamma_curve", "esr_mask_iou",
     "esr_mask_dilate", "esr_edit_label",
+    "esr_ray_filter",
 ]
 
 # full ctypes signatures (argument conversion checked on every call) of the entries that declare them
@@ -169,6 +170,8 @@ SIGNATURES = {
     "esr_edit_label": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
+    "esr_ray_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_int32,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

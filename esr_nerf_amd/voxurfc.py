@@ -21,6 +21,7 @@ import torch.nn as nn
 from . import _lib, render_utils
 from .fine_engine import DX_ROWS, FineEngine, _Workspace, make_scene
 from .modules import DenseGrid, ForwardSwitch, Gaussian3DConv, GradientConv, MaskCache, _linears, _mlp_stack
+from .voxurff import VoxurfF
 
 KIND_COARSE = 4
 XC_ROWS, HID = 72, 128
@@ -275,7 +276,9 @@ class VoxurfC(ForwardSwitch, nn.Module):
         return self._engine
 
     def scene_struct(self):
-        return make_scene(self._xyz_cache[0], self._xyz_cache[1], self.mask_xyz_min.tolist(), self.mask_xyz_max.tolist(),
+        if not hasattr(self, "_mask_box"):      # host copy: tolist() of a device tensor is a sync each
+            self._mask_box = (self.mask_xyz_min.tolist(), self.mask_xyz_max.tolist())
+        return make_scene(self._xyz_cache[0], self._xyz_cache[1], self._mask_box[0], self._mask_box[1],
                           self._world_size_l, list(self.mask_cache.density.shape[2:]), self.near, self._stepdist,
                           self._voxel_size_f, self.mask_cache.act_shift, self.maskcache_thres, self.fastcolor_thres,
                           self.s_val, [0.5, 1.0, 1.5, 2.0])
@@ -372,6 +375,29 @@ class VoxurfC(ForwardSwitch, nn.Module):
             rays_o.contiguous(), rays_d.contiguous(), self.xyz_min, self.xyz_max, self.near, 1e9, stepdist)[:4]
         keep = ~out_box
         return pts[keep], ray_id[keep], step_id[keep]
+
+    # ------------------------------------------------------------------ data filtering (coarse.py:208)
+    # voxurfc.py:448-481 and voxurff.py:504-537 are the same text: one restatement serves both classes
+    sample_ray_ori = VoxurfF.sample_ray_ori
+
+    def filter_training_rays_in_maskcache_sampling(self, rays_o: torch.Tensor, rays_d: torch.Tensor, chunk_size: int):
+        """True for rays with at least one in-box sample inside the mask cache (voxurfc.py:426-446).  The coarse renderer
+        always uses the fixed-count sampler ``sample_ray_ori``.  Device tensors go through ONE launch of esr_ray_filter
+        over all rays (rayfilter.py; ``chunk_size`` does not touch device work), CPU tensors through
+        ``_filter_rays_torch``."""
+        from . import rayfilter
+        return rayfilter.filter_training_rays(self, rays_o, rays_d, chunk_size, fixed=True)
+
+    @torch.no_grad()
+    def _filter_rays_torch(self, rays_o, rays_d, chunk_size: int):
+        """The reference's chunk loop in torch ops (what runs for CPU tensors)."""
+        dev = rays_o.device
+        keep_all = torch.ones(len(rays_o), dtype=torch.bool, device=dev)
+        for idx in torch.arange(len(rays_o), device=dev).split(chunk_size):
+            pts, out, _ = self.sample_ray_ori(rays_o[idx], rays_d[idx])
+            out[~out] |= ~self.mask_cache(pts[~out])
+            keep_all[idx] &= (~out).any(-1)
+        return keep_all
 
     def extract_geometry(self, resolution: int = 512, threshold: float = 0.0, batch_size: int = 64, smooth: bool = True,
                          sigma: float = 0.5):

@@ -358,11 +358,20 @@ class VoxurfF(ForwardSwitch, nn.Module):
         out = miss[..., None] | ((self.xyz_min > pts) | (pts > self.xyz_max)).any(dim=-1)
         return pts, out, step
 
-    @torch.no_grad()
     def filter_training_rays_in_maskcache_sampling(self, rays_o, rays_d, chunk_size: int):
         """True for rays with at least one in-box sample inside the mask cache (voxurff.py:463-502).  Two branches, as
         in the reference: with ``sdf_random_init`` the fixed-count sampler ``sample_ray_ori`` (t-range clamped to
-        near/far), otherwise the march sampler with far = 1e9; they keep different ray sets."""
+        near/far), otherwise the march sampler with far = 1e9; they keep different ray sets.  Device tensors go through
+        ONE launch of esr_ray_filter over all rays (rayfilter.py; ``chunk_size`` does not touch device work), CPU tensors
+        through ``_filter_rays_torch``."""
+        from . import rayfilter
+        return rayfilter.filter_training_rays(self, rays_o, rays_d, chunk_size, fixed=bool(self.sdf_random_init))
+
+    @torch.no_grad()
+    def _filter_rays_torch(self, rays_o, rays_d, chunk_size: int):
+        """The reference's chunk loop in torch ops: every sample of a chunk materialised, compacted by boolean mask,
+        ``MaskCache.forward`` on the survivors.  What runs for CPU tensors, and what tools/ray_filter_time.py times the
+        kernel against."""
         dev = rays_o.device
         keep_all = torch.ones(len(rays_o), dtype=torch.bool, device=dev)
         for idx in torch.arange(len(rays_o), device=dev).split(chunk_size):

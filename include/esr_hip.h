@@ -1255,6 +1255,30 @@ int esr_edit_label(const float *esp, int64_t n, const float *w2c, float focal, i
                    int32_t n_cond, const int64_t *cond_modes, const float *cond_intensities, const float *cond_colors,
                    uint8_t *keep, int64_t *em_modes, float *em_colors, float *em_intensities, float *uv, void *stream);
 
+/* ------------------------------------------------------------------------- *
+ * L. Training-ray filter (filter_training_rays_in_maskcache_sampling)
+ * ------------------------------------------------------------------------- */
+
+#define ESR_RAY_FILTER_MARCH 0   /* the march sampler, far = 1e9 (render_utils_kernel.cu:12-79,167-194)                   */
+#define ESR_RAY_FILTER_FIXED 1   /* sample_ray_ori: t-range clamped to [near, far], n_samples steps for every ray          */
+
+/*
+ * keep[r] = 1 when some in-box sample of ray r lies inside the mask cache -- replaces the chunk loops of
+ * app/coarse/model/voxurfc.py:426-446 (with sample_ray_ori, :448-481) and app/fine/model/voxurff.py:463-502 (both
+ * branches; sample_ray_ori :504-537) and MaskCache.forward (app/utils/base/module.py:104-114) inside them.
+ * scene: xyz_min / xyz_max, mask_min / mask_max, mx / my / mz, near_, stepdist (= stepsize * voxel_size in f32), act_shift
+ * and mask_thres are read.  mask_density [mx,my,mz] f32 (max-pooled), rays_o / rays_d [n_rays,3] f32.
+ * mode ESR_RAY_FILTER_MARCH: every step 0 .. n_steps - 1 of the march sampler with far = 1e9 (far_ and n_samples are not
+ * read); there is NO per-ray step cap (unlike esr_fine_march_count's scene.max_steps).  mode ESR_RAY_FILTER_FIXED: far_ =
+ * the model's far, n_samples [host] = int(|grid_shape + 1| / stepsize) + 1; a ray with t_max <= t_min is dropped.
+ * keep u8 [n_rays]; first_hit (or NULL) i32 [n_rays]: the index of the first kept step, -1 for a dropped ray.
+ * n_rays == 0 launches nothing.  One wave per ray, no atomics, no workspace: the same bytes on every call.  Arithmetic
+ * order of both samplers: the header of csrc/rayfilter.hip.
+ */
+int esr_ray_filter(const esr_scene_t *scene, const float *mask_density, const float *rays_o, const float *rays_d,
+                   int64_t n_rays, int32_t mode, float far_, int32_t n_samples, uint8_t *keep, int32_t *first_hit,
+                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif
