@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libesr_hip.so")
 # developer experiments only (python -m esr_nerf_amd.build --variant builds alternative libraries; tools/ab_env.sh times them
 # side by side on one box)
 LIB_PATH = os.environ.get("ESR_LIB_PATH", LIB_PATH)
-ABI_VERSION = 30
+ABI_VERSION = 31
 _lib = None
 
 
@@ -162,6 +162,7 @@ EXPORTS = [
     "esr_ssim", "esr_view_post", "esr_sqerr_sum", "esr_gamma_curve", "esr_mask_iou",
     "esr_mask_dilate", "esr_edit_label",
     "esr_ray_filter",
+    "esr_adam_step_live", "esr_brick_live_from_moments",
 ]
 
 # full ctypes signatures (argument conversion checked on every call) of the entries that declare them
@@ -172,6 +173,10 @@ SIGNATURES = {
                                  C.c_void_p, C.c_void_p]),
     "esr_ray_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esr_adam_step_live": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_void_p]),
+    "esr_brick_live_from_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
 }
 
 

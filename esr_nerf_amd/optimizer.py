@@ -8,6 +8,13 @@ channels-last (colour grids) are updated in their storage order -- Adam is eleme
 order gives the same values; moments restored from a reference checkpoint arrive contiguous
 (``Optimizer.load_state_dict`` keeps the loaded strides) and are brought into the parameter's order first.
 
+``Adam(..., live_bricks=True)`` (or ``ESR_ADAM_LIVE=1`` through ``create_optimizer_or_freeze_model``) updates the large
+tensors -- the grids -- brick by brick with ``esr_adam_step_live``: a 512-byte brick whose gradient has never been
+non-zero and whose moments are zero is skipped after the gradient read, because the update is the identity there
+("Live-brick Adam"); parameters and state stay ``torch.equal`` to the dense optimizer's, the
+``state_dict`` is the same.  With ``zero_grads=True`` the same pass zeroes the gradient bricks it found non-zero, and
+``take_zeroed`` tells the trainer step (``_Step.zero_fill_by``) which part of its buffer needs no memset.
+
 ``CosineLR`` is the trainers' learning-rate schedule (optimizer.py:231-275): warm-up then half cosine, handed
 out as the multiplicative step-to-step factor the trainers apply to every group's lr.
 """
@@ -15,6 +22,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 
 import torch
 import torch.nn as nn
@@ -22,8 +30,15 @@ import torch.nn as nn
 from . import _lib
 
 
-def create_optimizer_or_freeze_model(model: nn.Module, **lrates: float):
-    """optimizer.py:11-60: one param group per named attribute with lr > 0, freeze the others."""
+LIVE_MIN_NUMEL = 1 << 20      # live mode: smaller tensors (the MLPs) take the dense kernel -- nothing to skip in them
+
+
+def create_optimizer_or_freeze_model(model: nn.Module, *, live_bricks=None, **lrates: float):
+    """optimizer.py:11-60: one param group per named attribute with lr > 0, freeze the others.  ``live_bricks``: the
+    ``Adam`` mode of that name; ``None`` reads the environment (``ESR_ADAM_LIVE=1`` turns it on: the reference's
+    trainers call this function with learning rates only)."""
+    if live_bricks is None:
+        live_bricks = os.environ.get("ESR_ADAM_LIVE", "0") == "1"
     groups = []
     for k, lr in lrates.items():
         if not hasattr(model, k):
@@ -38,7 +53,7 @@ def create_optimizer_or_freeze_model(model: nn.Module, **lrates: float):
         else:
             for p in (param.parameters() if isinstance(param, nn.Module) else [param]):
                 p.requires_grad = False
-    return Adam(groups, betas=(0.9, 0.99))
+    return Adam(groups, betas=(0.9, 0.99), live_bricks=bool(live_bricks))
 
 
 def _same_layout(a: torch.Tensor, b: torch.Tensor) -> bool:
@@ -62,8 +77,23 @@ def _flat_storage(t: torch.Tensor) -> torch.Tensor:
     raise RuntimeError("fused Adam needs densely stored parameters")
 
 
+def _mem_key(t: torch.Tensor):
+    """The memory a dense tensor occupies (whatever view of it is asked about)."""
+    return (t.device, t.data_ptr(), t.numel())
+
+
+class _Live:
+    """Side state of one parameter in live mode (never part of ``Adam.state``): the brick flags and the moments they
+    were built for."""
+    __slots__ = ("flags", "moments", "n")
+
+    def __init__(self, n, flags, moments):
+        self.n, self.flags, self.moments = n, flags, moments
+
+
 class Adam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False,
+                 live_bricks=False, zero_grads=False):
         if amsgrad:
             raise NotImplementedError("amsgrad is never enabled by the reference and is not on the HIP path")
         if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0 \
@@ -71,6 +101,10 @@ class Adam(torch.optim.Optimizer):
             raise ValueError("invalid Adam hyper-parameter")
         self.per_lr = None
         self._per_lr_for = {}            # id(param) -> per_lr in that parameter's storage order (built once)
+        self.live_bricks, self.zero_grads = bool(live_bricks), bool(zero_grads)
+        self._live = {}                  # id(param) -> _Live (flags rebuilt from the moments whenever they are replaced)
+        self._stats = {}                 # device -> int64 [parameters, 2]: the live kernel's counters, zeroed once per step
+        self._zeroed = set()             # _mem_key of the gradients the last step() left all-zero
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False))
         self.name2pg = {pg["name"]: pg for pg in self.param_groups if "name" in pg}
 
@@ -79,12 +113,87 @@ class Adam(torch.optim.Optimizer):
         for group in self.param_groups:
             group.setdefault("amsgrad", False)
         self.__dict__.setdefault("per_lr", None)
+        self.__dict__.setdefault("live_bricks", False)
+        self.__dict__.setdefault("zero_grads", False)
         self._per_lr_for = {}
+        self._live = {}                  # (rebuilt from the moments at the next step)
+        self._stats = {}
+        self._zeroed = set()
+
+    def __getstate__(self):
+        d = dict(super().__getstate__())          # (torch pickles defaults, state and param_groups only)
+        d["live_bricks"], d["zero_grads"] = self.live_bricks, self.zero_grads
+        return d
 
     def set_pervoxel_lr(self, count):
         assert self.param_groups[0]["params"][0].shape == count.shape
         self.per_lr = count.float() / count.max()
         self._per_lr_for = {}
+        # live mode skips bricks on the strength of 0 * per_lr == 0: checked here, once (one synchronisation)
+        if self.live_bricks and not bool(torch.isfinite(self.per_lr).all()):
+            raise ValueError("live_bricks needs a finite per-voxel learning rate")
+
+    # -- live bricks ----------------------------------------------------------------------------------------------------
+    def _live_ok(self, group, p, g, plr) -> bool:
+        """Whether this tensor takes esr_adam_step_live in this step (else: esr_adam_step, as without the mode)."""
+        if not self.live_bricks or p.numel() < LIVE_MIN_NUMEL or group["weight_decay"] != 0 or not group["eps"] > 0:
+            return False
+        if g is not p.grad:                                   # the gradient had to be re-stored in the parameter's order
+            return False
+        st = self.state[p]
+        ts = [p, g, st["exp_avg"], st["exp_avg_sq"]] + ([plr] if plr is not None else [])
+        return all(t.data_ptr() % 16 == 0 for t in ts)
+
+    def _live_for(self, p, st, L) -> "_Live":
+        """The parameter's flags, rebuilt from the moments when those are not the tensors the flags were kept for (first
+        step, load_state_dict, unpickling, state set by hand) or the parameter changed shape or device."""
+        n = p.numel()
+        lv = self._live.get(id(p))
+        m, v = st["exp_avg"], st["exp_avg_sq"]
+        if lv is not None and lv.n == n and lv.flags.device == p.device and lv.moments[0] is m and lv.moments[1] is v:
+            return lv
+        nb = -(-n // L.esr_brick_floats())
+        lv = self._live[id(p)] = _Live(n, torch.zeros(nb, dtype=torch.uint8, device=p.device), (m, v))
+        _lib.check(L.esr_brick_live_from_moments(_lib.ptr(_flat_storage(m)), _lib.ptr(_flat_storage(v)), n,
+                                                 _lib.ptr(lv.flags), _lib.stream_ptr(p.device)),
+                   "esr_brick_live_from_moments")
+        return lv
+
+    def _stats_row(self, i, device, fresh):
+        """Row ``i`` (the parameter's position over all groups) of the device's counter table; ``fresh``: first use in this
+        step() -- the table is zeroed, once for all its rows."""
+        t = self._stats.get(device)
+        if t is None or i >= t.shape[0]:                          # (first use, or a param group was added since)
+            fresh.discard(device)
+            t = self._stats[device] = torch.empty(sum(len(g["params"]) for g in self.param_groups), 2, dtype=torch.int64,
+                                                  device=device)
+        if device not in fresh:
+            fresh.add(device)
+            t.zero_()
+        return t[i]
+
+    def live_stats(self):
+        """{name or index: dict(bricks, live, grad)} of the tensors that took the live kernel in the last ``step()``: the
+        brick total, the live bricks, the bricks that had a non-zero gradient in that step.  The counters are read back
+        here, once per call and device, never inside ``step()``."""
+        out, host, i = {}, {d: t.tolist() for d, t in self._stats.items()}, 0
+        for group in self.param_groups:
+            for j, p in enumerate(group["params"]):
+                lv = self._live.get(id(p))
+                if lv is not None and p.device in host and i < len(host[p.device]):
+                    key = i if "name" not in group else group["name"] if len(group["params"]) == 1 else f"{group['name']}.{j}"
+                    live, grad = host[p.device][i]
+                    out[key] = dict(bricks=int(lv.flags.numel()), live=int(live), grad=int(grad))
+                i += 1
+        return out
+
+    def take_zeroed(self, t: torch.Tensor) -> bool:
+        """Whether the last ``step()`` left the gradient memory ``t`` all-zero (``zero_grads``); asking consumes the mark."""
+        k = _mem_key(t)
+        if k in self._zeroed:
+            self._zeroed.discard(k)
+            return True
+        return False
 
     def load_state_dict(self, state_dict):
         """torch keeps the strides of the LOADED moments; a checkpoint written by the reference (fine.py:254-255)
@@ -106,9 +215,12 @@ class Adam(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         L = _lib.lib()
+        self._zeroed.clear()
+        fresh, i = set(), -1
         for group in self.param_groups:
             beta1, beta2 = group["betas"]
             for p in group["params"]:
+                i += 1
                 if p.grad is None:
                     continue
                 if not p.is_cuda:
@@ -130,6 +242,19 @@ class Adam(torch.optim.Optimizer):
                     if plr is None:
                         plr = self._per_lr_for[id(p)] = _like_param(p, self.per_lr.to(device=p.device, dtype=p.dtype))
                 pf, gf, mf, vf = _flat_storage(p), _flat_storage(g), _flat_storage(st["exp_avg"]), _flat_storage(st["exp_avg_sq"])
+                if self._live_ok(group, p, g, plr):
+                    lv = self._live_for(p, st, L)
+                    stats = self._stats_row(i, p.device, fresh)
+                    rc = L.esr_adam_step_live(_lib.ptr(pf), _lib.ptr(gf), _lib.ptr(mf), _lib.ptr(vf),
+                                              _lib.ptr(_flat_storage(plr)) if plr is not None else None,
+                                              _lib.ptr(lv.flags), pf.numel(), group["lr"], beta1, beta2, group["eps"],
+                                              int(st["step"]), int(self.zero_grads), _lib.ptr(stats),
+                                              _lib.stream_ptr(p.device))
+                    _lib.check(rc, "esr_adam_step_live")
+                    if self.zero_grads:
+                        self._zeroed.add(_mem_key(gf))
+                    continue
+                self._live.pop(id(p), None)             # (a dense step moves moments the flags know nothing about)
                 rc = L.esr_adam_step(_lib.ptr(pf), _lib.ptr(gf), _lib.ptr(mf), _lib.ptr(vf),
                                      _lib.ptr(_flat_storage(plr)) if plr is not None else None,
                                      C.c_int64(pf.numel()), C.c_float(group["lr"]), C.c_float(beta1), C.c_float(beta2),
@@ -153,7 +278,8 @@ class ShardedGridAdam:
     the fused Adam on this rank's shard only -> ``all_gather`` of the updated parameters.  The moments exist for the
     owned shard only (1/G of the dense optimizer's memory and update traffic).  Same arithmetic as ``Adam`` above
     (``esr_adam_step``), per-attribute learning rates by position in the flat buffer; a per-voxel lr is not supported
-    (only the alphamask pre-stage of the reference uses one).  ``adam_fn``: test double for CPU rehearsals."""
+    (only the alphamask pre-stage of the reference uses one).  The live-brick mode of ``Adam`` is not provided here:
+    the shard is updated densely.  ``adam_fn``: test double for CPU rehearsals."""
 
     def __init__(self, grids, lrs, betas=(0.9, 0.99), eps=1e-8, adam_fn=None):
         self.grids = grids

@@ -79,6 +79,7 @@ class _Step:
         self.sync_mode_used = None        # the exchange of the last data-parallel step (bench.py: grad_exchange.mode)
         self._sync_mode = os.environ.get("ESR_GRAD_SYNC", "auto")       # read once, here
         self._sync = None                 # grad_sync.GridGradSync of the sparse exchange (built by its first step)
+        self.zero_fill_by = None          # optimizer.Adam(live_bricks=True, zero_grads=True) that trains this step's grids
         self._names = None
         self._flat = None
         self._n_grid = self._n_grid_pad = 0
@@ -124,7 +125,10 @@ class _Step:
         vkey = (X, Y, Z, id(self.sharded))          # (a ShardedGrids attached later changes the padding)
         v = self._views
         if v is not None and v[0] == vkey and v[1] is self._flat:
-            self._flat.zero_()
+            if self.zero_fill_by is None:
+                self._flat.zero_()
+            else:
+                self._zero_unmarked(v[2])
             return dict(v[2])
         params = dict(m.named_parameters())
         shapes = [(f"{g}.grid", (1, 1, X, Y, Z) if g == "sdf" else (1, X, Y, Z, 6)) for g in self.GRIDS]
@@ -136,6 +140,8 @@ class _Step:
         if self._flat is None or self._flat.numel() != total:
             self._flat = torch.empty(total, dtype=torch.float32, device=dev)
         self._flat.zero_()
+        if self.zero_fill_by is not None and self._views is not None:
+            self._zero_unmarked(self._views[2], drop_only=True)
         out, o = {}, 0
         for i, (n, s) in enumerate(shapes):
             k = int(torch.Size(s).numel())
@@ -147,6 +153,26 @@ class _Step:
                 self._n_grid_pad = o
         self._views = (vkey, self._flat, dict(out))
         return out
+
+    def _zero_unmarked(self, views, drop_only=False):
+        """Zero the flat buffer except the grid ranges that ``zero_fill_by`` (optimizer.Adam with ``zero_grads``) left
+        all-zero in its last step: the live-brick kernel zeroed the bricks it found non-zero while it read them.  A mark
+        is consumed by asking, so only the first call after an optimizer step finds any: a second forward without a
+        step, the range fallback's second attempt or a frozen grid zero in full.  Runs of unmarked ranges -- with the
+        shard padding and the MLP / tail part behind the grids -- are zeroed together, one launch per run.
+        ``drop_only``: the buffer was zeroed in full (reallocation); marks left for the old views are discarded."""
+        opt, flat = self.zero_fill_by, self._flat
+        o = run = 0                       # [run, o): not yet zeroed, ends where the next marked grid begins
+        for g in self.GRIDS:
+            t = views[f"{g}.grid"]
+            k = t.numel()
+            if opt.take_zeroed(t) and not drop_only:
+                if o > run:
+                    flat[run:o].zero_()
+                run = o + k
+            o += k
+        if not drop_only and flat.numel() > run:
+            flat[run:].zero_()
 
     def _handout(self, G):
         """The colour grids' gradients as logical [1,6,X,Y,Z] views over their channels-last memory."""

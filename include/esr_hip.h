@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 30
+#define ESR_ABI_VERSION 31
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -947,6 +947,25 @@ int esr_eval_disp(const float *depth3, const float *alphainv_last, float far_, i
 int esr_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq,
                   const float *per_lr, int64_t n, float lr, float beta1, float beta2, float eps,
                   float weight_decay, int32_t step, void *stream);
+
+/*
+ * The same update restricted to LIVE bricks (bricks of esr_brick_floats() = 128 consecutive values, as section F; the last
+ * one may be ragged).  A brick is live once any of its gradients was non-zero (by value: -0.0 is zero) or its moments are;
+ * it stays live.  Bricks that are neither live nor have a non-zero gradient in this call are skipped after the gradient
+ * read: with g == m == v == 0, no weight decay, eps > 0 and a finite per_lr the update is the identity, so param,
+ * exp_avg and exp_avg_sq hold the bytes esr_adam_step would have left.
+ *   live:      [ceil(n/128)] bytes, read and updated (0 -> 1 only)
+ *   zero_grad: non-zero = write zeros over every gradient brick that held a non-zero value (the buffer is all-zero after)
+ *   stats:     NULL or int64[2]:  stats[0] += live bricks after the call, stats[1] += bricks with a non-zero gradient
+ * There is no weight decay.  All pointers 16-byte aligned; ESR_EINVAL otherwise, for eps <= 0, and for what
+ * esr_adam_step rejects.
+ *   esr_brick_live_from_moments: live[b] |= any(exp_avg != 0 or exp_avg_sq != 0) over brick b (after a state load)
+ */
+int esr_adam_step_live(float *param, float *grad, float *exp_avg, float *exp_avg_sq, const float *per_lr,
+                       uint8_t *live, int64_t n, float lr, float beta1, float beta2, float eps, int32_t step,
+                       int32_t zero_grad, int64_t *stats, void *stream);
+int esr_brick_live_from_moments(const float *exp_avg, const float *exp_avg_sq, int64_t n, uint8_t *live,
+                                void *stream);
 
 /*
  * Smoothed-gradient TV term of the fine / lts trainers, forward and backward -- replaces the dense torch chain
