@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libesr_hip.so")
 # developer experiments only (python -m esr_nerf_amd.build --variant builds alternative libraries; tools/ab_env.sh times them
 # side by side on one box)
 LIB_PATH = os.environ.get("ESR_LIB_PATH", LIB_PATH)
-ABI_VERSION = 31
+ABI_VERSION = 32
 _lib = None
 
 
@@ -117,6 +117,14 @@ class EsrViewPost(C.Structure):         # esr_view_post_t
                                           "sqerr")]
 
 
+class EsrCamera(C.Structure):           # esr_camera_t
+    _fields_ = [(n, C.c_float) for n in ("fx", "fy", "cx", "cy")] + [(n, C.c_int32) for n in ("width", "height", "n_views")]
+
+
+CAMERA_LDS_VIEWS = 256                  # ESR_CAMERA_LDS_VIEWS
+CAMERA_BOUNDS_BLOCKS = 1024             # ESR_CAMERA_BOUNDS_BLOCKS
+
+
 class EsrMlpWeights(C.Structure):
     _fields_ = [("w", C.c_void_p * 4), ("b", C.c_void_p * 4)]
 
@@ -163,6 +171,7 @@ EXPORTS = [
     "esr_mask_dilate", "esr_edit_label",
     "esr_ray_filter",
     "esr_adam_step_live", "esr_brick_live_from_moments",
+    "esr_camera_rays", "esr_camera_batch", "esr_camera_bounds", "esr_ray_filter_cameras",
 ]
 
 # full ctypes signatures (argument conversion checked on every call) of the entries that declare them
@@ -177,6 +186,14 @@ SIGNATURES = {
                                      C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_void_p,
                                      C.c_void_p]),
     "esr_brick_live_from_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "esr_camera_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
+    "esr_camera_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float,
+                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    "esr_camera_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esr_ray_filter_cameras": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

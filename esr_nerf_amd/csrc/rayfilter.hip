@@ -27,7 +27,16 @@
 // so a ray's 24 B come through the scalar cache and the per-ray geometry lives in scalar registers.  Streamed traffic is
 // 24 B read and 1 B (5 B) written per ray; the mask grid (a few tens of MB at the reference's resolution) is gathered from
 // L2 / Infinity Cache.  Few enough vector registers for eight waves per SIMD (tests/test_ray_filter_isa.py).
-#include "esr_common.h"
+//
+// Ray source.  The kernel body is a template over where a ray comes from: ArrayRays loads it from rays_o / rays_d
+// (esr_ray_filter), CameraRays makes it from (view, pixel) with the device function of camera_ray.h
+// (esr_ray_filter_cameras: no ray array is read at all, 1 B (5 B) of traffic per ray).  The row, hence view and pixel, is
+// wave-uniform, so the pose comes through the scalar cache as the array ray does.  Each source has its own __global__ entry
+// around the one body, so the array kernels keep their symbols and their code: 58 (fixed) / 57 (march) vector registers, no
+// scratch, eight waves per SIMD, before and after the body became a template.  The camera kernels: 48 / 46 vector registers, no
+// scratch; the march instantiation fits eight waves per SIMD, the fixed one SEVEN: its wave-uniform ray arithmetic lives in
+// scalar registers and takes 99 of them, three more than eight waves leave each (tools/kernel_meta.py).
+#include "camera_ray.h"
 
 #include <math.h>
 
@@ -85,8 +94,29 @@ __device__ __forceinline__ void fixed_point(const float o[3], const float d[3], 
     for (int a = 0; a < 3; ++a) p[a] = o[a] + d[a] * t;
 }
 
-template <bool FIXED>
-__global__ void __launch_bounds__(RF_THREADS) ray_filter_kernel(FilterParams P)
+struct ArrayRays {
+    const float *rays_o, *rays_d;
+    __device__ __forceinline__ void load(int64_t r, float o[3], float d[3]) const
+    {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { o[a] = rays_o[3 * r + a]; d[a] = rays_d[3 * r + a]; }
+    }
+};
+
+struct CameraRays {
+    esr_camera_t cam;
+    const float *poses;
+    __device__ __forceinline__ void load(int64_t r, float o[3], float d[3]) const
+    {
+        const int hw = cam.width * cam.height, row = (int)r;          // (the host refuses sets of 2^31 rays or more)
+        const int view = row / hw;
+        float vd[3];
+        esr_camera_ray_at(cam, poses, view, row - view * hw, o, d, vd);
+    }
+};
+
+template <bool FIXED, class SRC>
+__device__ __forceinline__ void ray_filter_body(const FilterParams &P, const SRC &src)
 {
     const esr_scene_t &sc = P.sc;
     const int lane = esr_lane();
@@ -96,19 +126,17 @@ __global__ void __launch_bounds__(RF_THREADS) ray_filter_kernel(FilterParams P)
     // (wave-uniform by construction; readfirstlane tells the compiler)
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     for (int64_t r = (int64_t)blockIdx.x * waves_per_blk + wave; r < P.n_rays; r += n_waves) {
-        const float *ro = P.rays_o + 3 * r, *rd = P.rays_d + 3 * r;
         int n_steps;
         float o[3], d[3], tmin = 0.f, nrm = 1.f;
         RayGeom g;
+        src.load(r, o, d);
         if (FIXED) {
             float tmax;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) { o[a] = ro[a]; d[a] = rd[a]; }
             fixed_trange(o, d, sc, P.far_, tmin, tmax);
             nrm = esr_ray_norm(d);
             n_steps = (tmax <= tmin) ? 0 : P.n_samples;
         } else {
-            g = esr_ray_geom(ro, rd, 0, sc.xyz_min, sc.xyz_max, sc.near_, 1e9f, sc.stepdist);
+            g = esr_ray_geom(o, d, 0, sc.xyz_min, sc.xyz_max, sc.near_, 1e9f, sc.stepdist);
             n_steps = g.n_steps;
         }
         int first = -1;
@@ -133,6 +161,18 @@ __global__ void __launch_bounds__(RF_THREADS) ray_filter_kernel(FilterParams P)
     }
 }
 
+template <bool FIXED>
+__global__ void __launch_bounds__(RF_THREADS) ray_filter_kernel(FilterParams P)
+{
+    ray_filter_body<FIXED>(P, ArrayRays{P.rays_o, P.rays_d});
+}
+
+template <bool FIXED>
+__global__ void __launch_bounds__(RF_THREADS) camera_filter_kernel(FilterParams P, CameraRays src)
+{
+    ray_filter_body<FIXED>(P, src);
+}
+
 }  // namespace
 
 ESR_API int esr_ray_filter(const esr_scene_t *scene, const float *mask_density, const float *rays_o, const float *rays_d,
@@ -153,6 +193,32 @@ ESR_API int esr_ray_filter(const esr_scene_t *scene, const float *mask_density, 
         ray_filter_kernel<true><<<grid, RF_THREADS, 0, esr_stream(stream)>>>(P);
     else
         ray_filter_kernel<false><<<grid, RF_THREADS, 0, esr_stream(stream)>>>(P);
+    ESR_CHECK_LAUNCH();
+    return 0;
+}
+
+ESR_API int esr_ray_filter_cameras(const esr_scene_t *scene, const float *mask_density, const esr_camera_t *cam,
+                                   const float *poses, int32_t mode, float far_, int32_t n_samples, uint8_t *keep,
+                                   int32_t *first_hit, void *stream)
+{
+    if (!scene || !cam || (mode != ESR_RAY_FILTER_MARCH && mode != ESR_RAY_FILTER_FIXED)) return ESR_EINVAL;
+    if (mode == ESR_RAY_FILTER_FIXED && n_samples < 0) return ESR_EINVAL;
+    if (cam->width < 1 || cam->height < 1 || cam->n_views < 0 || !(cam->fx != 0.f) || !(cam->fy != 0.f)) return ESR_EINVAL;
+    const int64_t n_rays = (int64_t)cam->n_views * cam->width * cam->height;
+    if (n_rays >= ((int64_t)1 << 31)) return ESR_EINVAL;
+    if (!n_rays) return 0;
+    if (!mask_density || !poses || !keep) return ESR_EINVAL;
+    if (scene->mx < 1 || scene->my < 1 || scene->mz < 1) return ESR_EINVAL;
+    FilterParams P;
+    P.sc = *scene;
+    P.mask_density = mask_density; P.rays_o = nullptr; P.rays_d = nullptr;
+    P.n_rays = n_rays; P.far_ = far_; P.n_samples = n_samples; P.keep = keep; P.first_hit = first_hit;
+    const CameraRays src{*cam, poses};
+    const int grid = esr_grid_for(n_rays, RF_THREADS / ESR_WAVE);
+    if (mode == ESR_RAY_FILTER_FIXED)
+        camera_filter_kernel<true><<<grid, RF_THREADS, 0, esr_stream(stream)>>>(P, src);
+    else
+        camera_filter_kernel<false><<<grid, RF_THREADS, 0, esr_stream(stream)>>>(P, src);
     ESR_CHECK_LAUNCH();
     return 0;
 }

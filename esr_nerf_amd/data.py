@@ -47,18 +47,29 @@ class BatchSampler:
                  data_idxs: Optional[torch.Tensor] = None, rank: int = 0, world: int = 1):
         self.cfg = cfg
         self.device = cfg.system.device
-        self.data_preload_to_cpu = _preload_to_cpu(cfg)
+        self.data_preload_to_cpu = self._preload(cfg)
         self.home = "cpu" if self.data_preload_to_cpu else self.device
         self.keys = keys
         self.batch_size = batch_size
         self.batch_st = batch_st
         self.rank, self.world = rank, world
-        n = len(data[keys[0]])
+        n = self._adopt(data)
         idx = torch.arange(n) if data_idxs is None else data_idxs
         self.data_idxs = (_pin(idx) if self.data_preload_to_cpu else idx.to(self.device)).contiguous()
-        self.data = {k: (_pin(data[k]) if self.data_preload_to_cpu else data[k].to(self.device).contiguous())
-                     for k in keys}
         self.data_num = len(self.data_idxs)
+
+    _preload = staticmethod(_preload_to_cpu)
+
+    def _adopt(self, data) -> int:
+        """Take the ray set in (``self.data``); returns its number of rows."""
+        self.data = {k: (_pin(data[k]) if self.data_preload_to_cpu else data[k].to(self.device).contiguous())
+                     for k in self.keys}
+        return len(self.data[self.keys[0]])
+
+    def _gather(self, rows: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """The batch dictionary of the original rows ``rows``, on the device: one row gather per key here; the camera
+        samplers (camera.py) override this method alone."""
+        return {k: self.data[k][rows].to(self.device, non_blocking=True) for k in self.keys}
 
     def shuffle(self):
         # the same draw as the reference (:81 / :86): a permutation of the CURRENT order
@@ -83,8 +94,7 @@ class BatchSampler:
         b_st = self.batch_st
         self.batch_st = b_en
         lo, hi = _share(b_st, b_en, self.rank, self.world)
-        rows = self.data_idxs[lo:hi]
-        return {k: self.data[k][rows].to(self.device, non_blocking=True) for k in self.keys}
+        return self._gather(self.data_idxs[lo:hi])
 
 
 class RayGroupManager:
@@ -94,18 +104,27 @@ class RayGroupManager:
                  rank: int = 0, world: int = 1):
         self.cfg = cfg
         self.device = cfg.system.device
-        self.data_preload_to_cpu = _preload_to_cpu(cfg)
+        self.data_preload_to_cpu = self._preload(cfg)
         self.home = "cpu" if self.data_preload_to_cpu else self.device
         self.keys = keys
         self.uncert_batch_size, self.cert_batch_size = uncert_batch_size, cert_batch_size
         self.uncert_batch_st, self.cert_batch_st = uncert_batch_st, cert_batch_st
         self.rank, self.world = rank, world
-        n = len(data[keys[0]])
-        u = torch.arange(n) if uncert_data_idxs is None else uncert_data_idxs
+        self.n_rows = self._adopt(data)
+        u = torch.arange(self.n_rows) if uncert_data_idxs is None else uncert_data_idxs
         c = torch.arange(0) if cert_data_idxs is None else cert_data_idxs
-        place = (lambda t: _pin(t)) if self.data_preload_to_cpu else (lambda t: t.to(self.device).contiguous())
-        self.uncert_data_idxs, self.cert_data_idxs = place(u), place(c)
-        self.data = {k: place(data[k]) for k in keys}
+        self.uncert_data_idxs, self.cert_data_idxs = self._place(u), self._place(c)
+
+    _preload = staticmethod(_preload_to_cpu)
+    _gather = BatchSampler._gather
+
+    def _place(self, t: torch.Tensor) -> torch.Tensor:
+        return _pin(t) if self.data_preload_to_cpu else t.to(self.device).contiguous()
+
+    def _adopt(self, data) -> int:
+        """Take the ray set in (``self.data``); returns its number of rows."""
+        self.data = {k: self._place(data[k]) for k in self.keys}
+        return len(self.data[self.keys[0]])
 
     @property
     def uncert_data_num(self) -> int:
@@ -140,8 +159,7 @@ class RayGroupManager:
         """``data[key]`` becomes a NEW full-length array: ``values`` at the original rows ``rows``, ``fill`` elsewhere -- what
         the reference's ``uncert_data[key] = values; cert_data[key] = fill`` (pdra.py:1030-1042) means for arrays that stay
         at their original rows.  The array it replaces (which may be the dataset's own) is not written."""
-        n = len(self.data[self.keys[0]])
-        full = torch.full((n, *values.shape[1:]), fill, dtype=values.dtype, device=self.home)
+        full = torch.full((self.n_rows, *values.shape[1:]), fill, dtype=values.dtype, device=self.home)
         full[rows.to(self.home)] = values.to(self.home)
         self.data[key] = _pin(full) if self.data_preload_to_cpu else full
 
@@ -166,7 +184,7 @@ class RayGroupManager:
         ul, uh = _share(u_st, u_en, self.rank, self.world)
         cl, ch = _share(c_st, c_en, self.rank, self.world)
         rows = torch.cat([self.uncert_data_idxs[ul:uh], self.cert_data_idxs[cl:ch]])
-        batch = {k: self.data[k][rows].to(self.device, non_blocking=True) for k in self.keys}
+        batch = self._gather(rows)
         um = torch.ones(rows.numel(), dtype=torch.bool, device=self.device)
         if c_en == c_st:
             um[:] = False          # reference quirk (:300): `mask[-0:] = False` clears the WHOLE mask when the

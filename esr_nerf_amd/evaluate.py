@@ -2,6 +2,7 @@
 (app/fine/fine.py:500-623, app/fine/pdra.py:600-762; the same loop in coarse.py / lts.py) without LPIPS, file writing
 and logging.
 
+``render_camera_view``  one view of a camera set (camera.py): its rays made on the device, then ``render_view``
 ``render_view``       the chunk loop (fine.py:553-570): every chunk's outputs go straight into one set of [H*W, C] buffers
 ``postprocess_view``  background, clamps, the ``lin/*_gamma`` twins (fine.py:572-587), optionally the uint8 images and the
                       squared-error sums against the targets in the same launches
@@ -46,6 +47,15 @@ def render_view(renderer, rays_o, rays_d, viewdirs, em_mode, pos_rt, height, wid
             bufs[k][s:e].copy_(v)
         del out                                     # one chunk's outputs at a time beside the buffers
     return {k: v.reshape(height, width, -1).squeeze(-1) for k, v in bufs.items()}
+
+
+@torch.no_grad()
+def render_camera_view(renderer, cams, view, em_mode, pos_rt, batch_size, **extra):
+    """``render_view`` of view ``view`` of the camera set ``cams`` (camera.Cameras): the view's rays come from one launch of
+    the ray kernel instead of a loader's arrays (the test phases' ``pose2ray``, data/esrnerf/esrnerf.py:237-238)."""
+    from .camera import camera_rays
+    rays_o, rays_d, viewdirs = camera_rays(cams, int(view))
+    return render_view(renderer, rays_o, rays_d, viewdirs, em_mode, pos_rt, cams.height, cams.width, batch_size, **extra)
 
 
 class ViewImages(dict):

@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 31
+#define ESR_ABI_VERSION 32
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -1297,6 +1297,69 @@ int esr_edit_label(const float *esp, int64_t n, const float *w2c, float focal, i
 int esr_ray_filter(const esr_scene_t *scene, const float *mask_density, const float *rays_o, const float *rays_d,
                    int64_t n_rays, int32_t mode, float far_, int32_t n_samples, uint8_t *keep, int32_t *first_hit,
                    void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * M. Camera-defined ray sets (rays made in the kernel from (view, pixel))
+ * ------------------------------------------------------------------------- */
+
+/*
+ * A set of n_views pinhole cameras that share their intrinsics and image size.  The ray of pixel p (i = p % width,
+ * j = p / width) of a view with the camera-to-world matrix R | t (poses [n_views,3,4] f32, one convention: a loader's
+ * `pose @ blender2opencv` is applied on the host):
+ *   px = ((i + 0.5) - cx) / fx, py = ((j + 0.5) - cy) / fy, d = R (px, py, 1), o = t, viewdir = d / max(|d|, 1e-12)
+ * in binary32 with correctly rounded division, every operation rounded on its own -- replaces pixelcoord / pose2ray /
+ * F.normalize of data/esrnerf/esrnerf.py:48-59,238,252-259 and data/dtu/dtu.py:74-86,194,207-211.  One device function
+ * (csrc/camera_ray.h) serves every entry below, so a ray is the same bits whichever of them made it.  A ray's row is
+ * view * height * width + pixel; n_views * height * width < 2^31 (else ESR_EINVAL).
+ */
+typedef struct {
+    float fx, fy, cx, cy;
+    int32_t width, height, n_views;
+} esr_camera_t;
+
+#define ESR_CAMERA_LDS_VIEWS 256        /* esr_camera_batch stages the pose table in LDS up to this many views (12 KB)  */
+#define ESR_CAMERA_BOUNDS_BLOCKS 1024   /* esr_camera_bounds: the most workgroup partials it writes (6 floats each)       */
+
+/*
+ * Dense rays of the views [v0, v1): rays_o, rays_d, viewdirs [(v1 - v0) * height * width, 3] f32 (16-byte aligned), in
+ * row order -- replaces pose2ray + F.normalize (esrnerf.py:237-238,252-259, dtu.py:193-194,207-211).  v0 == v1 launches
+ * nothing.  Plain stores, no atomics: the same bytes on every call.
+ */
+int esr_camera_rays(const esr_camera_t *cam, const float *poses, int32_t v0, int32_t v1, float *rays_o, float *rays_d,
+                    float *viewdirs, void *stream);
+/*
+ * The batch dictionary of n ray rows (rows i64 [n], any order, repeats allowed) in ONE launch -- replaces the five row
+ * gathers of a sampler's sample() over the arrays of esrnerf.py:233-248 / dtu.py:175-201.  Outputs rays_o, rays_d,
+ * viewdirs, rgbs [n,3] f32 and em_modes i64 [n] = view_modes[view] (view_modes i64 [n_views]: the training loaders give
+ * every ray of a view its view's mode, esrnerf.py:164-170, dtu.py:180-183).
+ * images: channels == 0: f32 [n_views*height*width, 3], already composited, gathered as it is; channels == 3 / 4: u8
+ * [n_views*height*width, channels].  A u8 value v becomes lut[v] (lut f32 [256] on the device: float32(arange(256) / 255.0)
+ * with the division in float64, `torch.FloatTensor(np.asarray(image) / 255.0)` of esrnerf.py:159-161); with 4 channels
+ * rgb = c * a + (1 - a) * white_bg, four separately rounded binary32 operations (esrnerf.py:235-236).  lut may be NULL and
+ * white_bg is not read when channels == 0.
+ * A row outside [0, n_views*height*width) reads nothing and yields NaN rays and colours and em_mode -1 (the host wrapper
+ * refuses such rows before the launch).  n == 0 launches nothing.
+ */
+int esr_camera_batch(const esr_camera_t *cam, const float *poses, const int64_t *view_modes, const void *images,
+                     int32_t channels, const float *lut, float white_bg, const int64_t *rows, int64_t n, float *rays_o,
+                     float *rays_d, float *viewdirs, float *rgbs, int64_t *em_modes, void *stream);
+/*
+ * Bounding box of the frustum points o + viewdir * near_ and o + viewdir * far_ over every ray of every view -- replaces
+ * the chunk loop of app/coarse/alphamask.py:108-122.  partials: f32 [ESR_CAMERA_BOUNDS_BLOCKS * 6] workspace (written
+ * and read by this call only); out f32 [6]: xyz_min then xyz_max.  Wave reduction, one partial per workgroup, a final
+ * one-workgroup pass; minimum and maximum do not depend on the order, so there are no atomics and the result is the
+ * same bytes on every call.  n_views == 0 yields +inf / -inf.
+ */
+int esr_camera_bounds(const esr_camera_t *cam, const float *poses, float near_, float far_, float *partials, float *out,
+                      void *stream);
+/*
+ * esr_ray_filter over every ray of every view, in row order, with each ray made by the device function above instead of
+ * loaded from arrays (the same kernel body; everything else as esr_ray_filter says, which replaces
+ * app/coarse/model/voxurfc.py:426-481 and app/fine/model/voxurff.py:463-537).  keep u8 [n_views*height*width], first_hit
+ * (or NULL) i32 of that length.  The flags equal esr_ray_filter's on the rays of esr_camera_rays bit for bit.
+ */
+int esr_ray_filter_cameras(const esr_scene_t *scene, const float *mask_density, const esr_camera_t *cam, const float *poses,
+                           int32_t mode, float far_, int32_t n_samples, uint8_t *keep, int32_t *first_hit, void *stream);
 
 #ifdef __cplusplus
 }
