@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libesr_hip.so")
 # developer experiments only (python -m esr_nerf_amd.build --variant builds alternative libraries; tools/ab_env.sh times them
 # side by side on one box)
 LIB_PATH = os.environ.get("ESR_LIB_PATH", LIB_PATH)
-ABI_VERSION = 32
+ABI_VERSION = 33
 _lib = None
 
 
@@ -34,6 +34,19 @@ class EsrScene(C.Structure):
 class EsrPlan(C.Structure):
     _fields_ = [(n, C.c_int32) for n in
                 ("n_on", "n_off", "tiles_on", "tiles_all", "m0", "m1", "m2", "overflow")]
+
+
+class EsrMarch(C.Structure):               # esr_march_t
+    _fields_ = [("scene", C.POINTER(EsrScene))] + \
+               [(n, C.c_void_p) for n in ("rays_o", "rays_d", "viewdirs", "mask_density", "sdf", "gg")] + \
+               [("n_rays", C.c_int32), ("flags", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("cnt3", "alphainv_last", "cum_weights", "ray_stats", "plan", "off3", "rec_ray",
+                                          "rec_step", "rec_w", "rec_sdf", "dweight", "dlast", "grad_sdf", "grad_gg",
+                                          "dsdf_rec")] + \
+               [("accumulate", C.c_int32), ("cache", C.c_void_p)]
+
+
+MARCH_COARSE, MARCH_GRAD_ALPHA = 1, 2      # ESR_MARCH_COARSE, ESR_MARCH_GRAD_ALPHA
 
 
 class EsrFeatArgs(C.Structure):
@@ -144,9 +157,8 @@ EXPORTS = [
     "esr_sample_count_f64", "esr_sample_fill_f64", "esr_alpha2weight_fwd_f64", "esr_alpha2weight_bwd_f64",
     "esr_infer_t_minmax", "esr_infer_n_samples", "esr_infer_ray_start_dir", "esr_sample_ndc_pts", "esr_sample_bg_pts",
     "esr_maskcache_lookup", "esr_raw2alpha", "esr_raw2alpha_bwd", "esr_tv_add_grad_masked",
-    "esr_fine_march_count", "esr_fine_plan_begin", "esr_fine_plan", "esr_fine_plan_totals", "esr_fine_plan_offsets", "esr_fine_march_fill",
-    "esr_fine_march_bwd", "esr_fine_march_bwd_rec", "esr_fine_march_cache_floats", "esr_fine_march_count_cached",
-    "esr_fine_march_fill_cached", "esr_fine_march_bwd_cached", "esr_fine_march_count_ga", "esr_fine_march_fill_ga", "esr_fine_march_bwd_ga",
+    "esr_march_count", "esr_march_fill", "esr_march_bwd", "esr_fine_march_cache_floats",
+    "esr_fine_plan_begin", "esr_fine_plan", "esr_fine_plan_totals", "esr_fine_plan_offsets",
     "esr_fine_feat_fwd", "esr_fine_feat_fwd_x16", "esr_fine_feat_x16_bytes", "esr_fine_feat_bwd",
     "esr_mlp_packed_floats", "esr_mlp_pack", "esr_mlp_pack_batch", "esr_mlp_packed_split_elems", "esr_mlp_split_gain_offset", "esr_mlp_split_range_flag", "esr_mlp_fwd_split", "esr_mlp_fwd_fine_split", "esr_mlp_dgrad_split", "esr_mlp_dgrad_fine_split", "esr_absmax", "esr_mlp_fwd", "esr_mlp_fwd_mixed", "esr_mlp_fwd_fine", "esr_mlp_dgrad_fine", "esr_mlp_fwd_fine_bf16", "esr_mlp_dgrad_fine_bf16", "esr_mlp_dgrad", "esr_mlp_wgrad", "esr_mlp_wgrad_batch", "esr_tone_wgrad_scratch_floats", "esr_tone_wgrad_recompute", "esr_tone_wgrad_recompute_bf16", "esr_tone_wgrad_recompute_split",
     "esr_mlp_wgrad_scratch_floats",
@@ -157,7 +169,6 @@ EXPORTS = [
     "esr_act_fwd", "esr_act_bwd", "esr_act_batch", "esr_lts_gather_rows_batch", "esr_pair_loss_batch", "esr_lts_ref_order_inv", "esr_lts_dirs_rays", "esr_composite3_fwd", "esr_composite3_bwd", "esr_lts_tone_in_bwd",
     "esr_sample_points", "esr_pair_loss_fwd_bwd", "esr_emit_edit",
     "esr_gauss3d_fwd", "esr_gauss3d_bwd", "esr_central_grad_fwd", "esr_central_grad_bwd",
-    "esr_coarse_march_count", "esr_coarse_march_fill", "esr_coarse_march_bwd", "esr_coarse_march_count_ga", "esr_coarse_march_fill_ga", "esr_coarse_march_bwd_ga",
     "esr_coarse_feat_fwd", "esr_coarse_feat_bwd", "esr_coarse_shade_fwd", "esr_coarse_shade_bwd",
     "esr_adam_step", "esr_eval_aux", "esr_eval_disp",
     "esr_mlp_packed_bf16_elems", "esr_mlp_pack_bf16", "esr_mlp_fwd_bf16", "esr_mlp_dgrad_bf16", "esr_mlp_wgrad_bf16",
@@ -176,6 +187,7 @@ EXPORTS = [
 
 # full ctypes signatures (argument conversion checked on every call) of the entries that declare them
 SIGNATURES = {
+    **{f"esr_march_{w}": (C.c_int, [C.POINTER(EsrMarch), C.c_void_p]) for w in ("count", "fill", "bwd")},
     "esr_mask_dilate": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "esr_edit_label": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -605,21 +605,6 @@ ESR_API int esr_fine_plan_begin(esr_plan_t *plan, void *stream)
     return (int)hipMemsetAsync(plan, 0, sizeof(esr_plan_t), esr_stream(stream));
 }
 
-ESR_API int esr_fine_march_count(const esr_scene_t *scene, const float *rays_o, const float *rays_d,
-                                 const float *mask_density, const float *sdf, int32_t n_rays,
-                                 int32_t *cnt3, float *alphainv_last, int32_t *ray_stats, esr_plan_t *plan,
-                                 void *stream)
-{
-    if (!scene || n_rays < 0 || !plan) return ESR_EINVAL;
-    if (n_rays && (!rays_o || !rays_d || !mask_density || !sdf || !cnt3 || !alphainv_last || !ray_stats))
-        return ESR_EINVAL;
-    MarchParams P = {};
-    P.sc = *scene; P.rays_o = rays_o; P.rays_d = rays_d; P.mask_density = mask_density; P.sdf = sdf;
-    P.n_rays = n_rays; P.cap = march_cap(scene); P.cnt3 = cnt3; P.alphainv_last = alphainv_last;
-    P.stats = ray_stats; P.plan = plan;
-    return launch_march<MARCH_COUNT>(P, esr_stream(stream));
-}
-
 ESR_API int esr_fine_plan(const int32_t *cnt3, const int64_t *em_modes, const int32_t *ray_stats,
                           int32_t n_rays, int32_t *off3, esr_plan_t *plan, void *stream)
 {
@@ -651,247 +636,55 @@ ESR_API int esr_fine_plan_offsets(const int32_t *cnt3, const int64_t *em_modes, 
     return 0;
 }
 
-ESR_API int esr_fine_march_fill(const esr_scene_t *scene, const float *rays_o, const float *rays_d,
-                                const float *mask_density, const float *sdf, int32_t n_rays,
-                                const int32_t *off3, int32_t *rec_ray, int32_t *rec_step, float *rec_w,
-                                float *rec_sdf, void *stream)
-{
-    if (!scene || n_rays < 0) return ESR_EINVAL;
-    if (n_rays && (!rays_o || !rays_d || !mask_density || !sdf || !off3 || !rec_ray || !rec_step ||
-                   !rec_w || !rec_sdf))
-        return ESR_EINVAL;
-    MarchParams P = {};
-    P.sc = *scene; P.rays_o = rays_o; P.rays_d = rays_d; P.mask_density = mask_density; P.sdf = sdf;
-    P.n_rays = n_rays; P.cap = march_cap(scene); P.off3 = off3; P.rec_ray = rec_ray;
-    P.rec_step = rec_step; P.rec_w = rec_w; P.rec_sdf = rec_sdf;
-    return launch_march<MARCH_FILL>(P, esr_stream(stream));
-}
-
-ESR_API int esr_fine_march_bwd(const esr_scene_t *scene, const float *rays_o, const float *rays_d,
-                               const float *mask_density, const float *sdf, int32_t n_rays,
-                               const int32_t *off3, const float *dweight, const float *dlast,
-                               float *grad_sdf, void *stream)
-{
-    if (!scene || n_rays < 0) return ESR_EINVAL;
-    if (n_rays && (!rays_o || !rays_d || !mask_density || !sdf || !off3 || !dweight || !dlast || !grad_sdf))
-        return ESR_EINVAL;
-    MarchParams P = {};
-    P.sc = *scene; P.rays_o = rays_o; P.rays_d = rays_d; P.mask_density = mask_density; P.sdf = sdf;
-    P.n_rays = n_rays; P.cap = march_cap(scene); P.off3 = off3; P.dweight = dweight; P.dlast = dlast;
-    P.grad_sdf = grad_sdf;
-    return launch_march<MARCH_BWD>(P, esr_stream(stream));
-}
-
-ESR_API int esr_fine_march_bwd_rec(const esr_scene_t *scene, const float *rays_o, const float *rays_d,
-                                   const float *mask_density, const float *sdf, int32_t n_rays,
-                                   const int32_t *off3, const float *dweight, const float *dlast,
-                                   float *grad_sdf, float *dsdf_rec, int32_t accumulate, void *stream)
-{
-    if (!scene || n_rays < 0) return ESR_EINVAL;
-    if (n_rays && (!rays_o || !rays_d || !mask_density || !sdf || !off3 || !dweight || !dlast || !grad_sdf || !dsdf_rec))
-        return ESR_EINVAL;
-    MarchParams P = {};
-    P.sc = *scene; P.rays_o = rays_o; P.rays_d = rays_d; P.mask_density = mask_density; P.sdf = sdf;
-    P.n_rays = n_rays; P.cap = march_cap(scene); P.off3 = off3; P.dweight = dweight; P.dlast = dlast;
-    P.grad_sdf = grad_sdf; P.dsdf_rec = dsdf_rec; P.dsdf_acc = accumulate;
-    return launch_march<MARCH_BWD>(P, esr_stream(stream));
-}
-
-// ---- the three passes sharing a cache (see MarchParams::cache) ----------------------------------------------------
 ESR_API int64_t esr_fine_march_cache_floats(const esr_scene_t *scene, int32_t n_rays)
 {
     if (!scene || n_rays < 0) return ESR_EINVAL;
     return (int64_t)n_rays * CACHE_ARR * march_cap(scene);
 }
 
-ESR_API int esr_fine_march_count_cached(const esr_scene_t *scene, const float *rays_o, const float *rays_d,
-                                        const float *mask_density, const float *sdf, int32_t n_rays, int32_t *cnt3,
-                                        float *alphainv_last, int32_t *ray_stats, esr_plan_t *plan, float *cache,
-                                        void *stream)
+namespace {
+
+MarchParams march_params(const esr_march_t &a)
 {
-    if (!scene || n_rays < 0 || !plan) return ESR_EINVAL;
-    if (n_rays && (!rays_o || !rays_d || !mask_density || !sdf || !cnt3 || !alphainv_last || !ray_stats || !cache))
-        return ESR_EINVAL;
     MarchParams P = {};
-    P.sc = *scene; P.rays_o = rays_o; P.rays_d = rays_d; P.mask_density = mask_density; P.sdf = sdf;
-    P.n_rays = n_rays; P.cap = march_cap(scene); P.cnt3 = cnt3; P.alphainv_last = alphainv_last;
-    P.stats = ray_stats; P.plan = plan; P.cache = cache;
-    return launch_march<MARCH_COUNT>(P, esr_stream(stream));
+    P.sc = *a.scene; P.rays_o = a.rays_o; P.rays_d = a.rays_d; P.viewdirs = a.viewdirs; P.mask_density = a.mask_density;
+    P.sdf = a.sdf; P.gg = a.gg; P.n_rays = a.n_rays; P.cap = march_cap(a.scene);
+    P.cnt3 = a.cnt3; P.alphainv_last = a.alphainv_last; P.cumw = a.cum_weights; P.stats = a.ray_stats; P.plan = a.plan;
+    P.off3 = a.off3; P.rec_ray = a.rec_ray; P.rec_step = a.rec_step; P.rec_w = a.rec_w; P.rec_sdf = a.rec_sdf;
+    P.dweight = a.dweight; P.dlast = a.dlast; P.grad_sdf = a.grad_sdf; P.grad_gg = a.grad_gg; P.dsdf_rec = a.dsdf_rec;
+    P.dsdf_acc = a.accumulate; P.cache = a.cache; P.last_in = a.alphainv_last;
+    return P;
 }
 
-ESR_API int esr_fine_march_fill_cached(const esr_scene_t *scene, const float *rays_o, const float *rays_d, int32_t n_rays,
-                                       const int32_t *off3, const int32_t *ray_stats, const float *cache,
-                                       int32_t *rec_ray, int32_t *rec_step, float *rec_w, float *rec_sdf, void *stream)
+// One pass of the march (include/esr_hip.h: esr_march_t): validate, copy, pick the instantiation from the flags.
+template <int MODE>
+int march(const esr_march_t *a, void *stream)
 {
-    if (!scene || n_rays < 0) return ESR_EINVAL;
-    if (n_rays && (!rays_o || !rays_d || !off3 || !ray_stats || !cache || !rec_ray || !rec_step || !rec_w || !rec_sdf))
+    if (!a || !a->scene || a->n_rays < 0 || (MODE == MARCH_COUNT && !a->plan)) return ESR_EINVAL;
+    const bool coarse = a->flags & ESR_MARCH_COARSE, ga = a->flags & ESR_MARCH_GRAD_ALPHA;
+    // what no instantiation serves: the cache and dsdf_rec are the fine "interp" march's (the kernel would read them under
+    // COARSE too), the gradient grids the coarse "grad" march's
+    if ((a->flags & ~(ESR_MARCH_COARSE | ESR_MARCH_GRAD_ALPHA)) || ((coarse || ga) && (a->cache || a->dsdf_rec)) ||
+        (!(coarse && ga) && (a->gg || a->grad_gg)))
         return ESR_EINVAL;
-    MarchParams P = {};
-    P.sc = *scene; P.rays_o = rays_o; P.rays_d = rays_d;
-    P.n_rays = n_rays; P.cap = march_cap(scene); P.off3 = off3; P.stats = const_cast<int32_t *>(ray_stats);
-    P.cache = const_cast<float *>(cache); P.rec_ray = rec_ray; P.rec_step = rec_step; P.rec_w = rec_w; P.rec_sdf = rec_sdf;
-    return launch_march<MARCH_FILL>(P, esr_stream(stream));
+    // the pointers this pass of this variant reads or writes; the cached fill and backward do not walk (no fields)
+    const bool walk = MODE == MARCH_COUNT || !a->cache;
+    bool ok = a->rays_o && a->rays_d;
+    if (walk) ok = ok && a->mask_density && a->sdf && (!ga || a->viewdirs) && (!(coarse && ga) || a->gg);
+    if (MODE == MARCH_COUNT) ok = ok && a->cnt3 && a->alphainv_last && a->ray_stats && (!coarse || a->cum_weights);
+    else ok = ok && a->off3 && (!a->cache || a->ray_stats);
+    if (MODE == MARCH_FILL) ok = ok && a->rec_ray && a->rec_step && a->rec_w && a->rec_sdf;
+    if (MODE == MARCH_BWD)
+        ok = ok && a->dweight && a->dlast && a->grad_sdf && (!a->cache || a->alphainv_last) && (!(coarse && ga) || a->grad_gg);
+    if (a->n_rays && !ok) return ESR_EINVAL;
+    MarchParams P = march_params(*a);
+    const hipStream_t s = esr_stream(stream);
+    if (coarse) return ga ? launch_march<MODE, true, true>(P, s) : launch_march<MODE, true>(P, s);
+    return ga ? launch_march<MODE, false, true>(P, s) : launch_march<MODE>(P, s);
 }
 
-ESR_API int esr_fine_march_bwd_cached(const esr_scene_t *scene, const float *rays_o, const float *rays_d, int32_t n_rays,
-                                      const int32_t *off3, const int32_t *ray_stats, const float *alphainv_last,
-                                      const float *cache, const float *dweight, const float *dlast, float *grad_sdf,
-                                      float *dsdf_rec, int32_t accumulate, void *stream)
-{
-    if (!scene || n_rays < 0) return ESR_EINVAL;
-    if (n_rays && (!rays_o || !rays_d || !off3 || !ray_stats || !alphainv_last || !cache || !dweight || !dlast || !grad_sdf))
-        return ESR_EINVAL;
-    MarchParams P = {};
-    P.sc = *scene; P.rays_o = rays_o; P.rays_d = rays_d;
-    P.n_rays = n_rays; P.cap = march_cap(scene); P.off3 = off3; P.stats = const_cast<int32_t *>(ray_stats);
-    P.last_in = alphainv_last; P.cache = const_cast<float *>(cache); P.dweight = dweight; P.dlast = dlast;
-    P.grad_sdf = grad_sdf; P.dsdf_rec = dsdf_rec; P.dsdf_acc = accumulate;
-    return launch_march<MARCH_BWD>(P, esr_stream(stream));
-}
+}  // namespace
 
-// ---- cfg neus_alpha: "grad" (functions.py:45-69): the same three entry points with the batch's view directions ----
-ESR_API int esr_fine_march_count_ga(const esr_scene_t *scene, const float *rays_o, const float *rays_d, const float *viewdirs,
-                                    const float *mask_density, const float *sdf, int32_t n_rays, int32_t *cnt3,
-                                    float *alphainv_last, int32_t *ray_stats, esr_plan_t *plan, void *stream)
-{
-    if (!scene || n_rays < 0 || !plan) return ESR_EINVAL;
-    if (n_rays && (!rays_o || !rays_d || !viewdirs || !mask_density || !sdf || !cnt3 || !alphainv_last || !ray_stats))
-        return ESR_EINVAL;
-    MarchParams P = {};
-    P.sc = *scene; P.rays_o = rays_o; P.rays_d = rays_d; P.viewdirs = viewdirs; P.mask_density = mask_density; P.sdf = sdf;
-    P.n_rays = n_rays; P.cap = march_cap(scene); P.cnt3 = cnt3; P.alphainv_last = alphainv_last;
-    P.stats = ray_stats; P.plan = plan;
-    return launch_march<MARCH_COUNT, false, true>(P, esr_stream(stream));
-}
-
-ESR_API int esr_fine_march_fill_ga(const esr_scene_t *scene, const float *rays_o, const float *rays_d, const float *viewdirs,
-                                   const float *mask_density, const float *sdf, int32_t n_rays, const int32_t *off3,
-                                   int32_t *rec_ray, int32_t *rec_step, float *rec_w, float *rec_sdf, void *stream)
-{
-    if (!scene || n_rays < 0) return ESR_EINVAL;
-    if (n_rays && (!rays_o || !rays_d || !viewdirs || !mask_density || !sdf || !off3 || !rec_ray || !rec_step ||
-                   !rec_w || !rec_sdf))
-        return ESR_EINVAL;
-    MarchParams P = {};
-    P.sc = *scene; P.rays_o = rays_o; P.rays_d = rays_d; P.viewdirs = viewdirs; P.mask_density = mask_density; P.sdf = sdf;
-    P.n_rays = n_rays; P.cap = march_cap(scene); P.off3 = off3; P.rec_ray = rec_ray;
-    P.rec_step = rec_step; P.rec_w = rec_w; P.rec_sdf = rec_sdf;
-    return launch_march<MARCH_FILL, false, true>(P, esr_stream(stream));
-}
-
-ESR_API int esr_fine_march_bwd_ga(const esr_scene_t *scene, const float *rays_o, const float *rays_d, const float *viewdirs,
-                                  const float *mask_density, const float *sdf, int32_t n_rays, const int32_t *off3,
-                                  const float *dweight, const float *dlast, float *grad_sdf, void *stream)
-{
-    if (!scene || n_rays < 0) return ESR_EINVAL;
-    if (n_rays && (!rays_o || !rays_d || !viewdirs || !mask_density || !sdf || !off3 || !dweight || !dlast || !grad_sdf))
-        return ESR_EINVAL;
-    MarchParams P = {};
-    P.sc = *scene; P.rays_o = rays_o; P.rays_d = rays_d; P.viewdirs = viewdirs; P.mask_density = mask_density; P.sdf = sdf;
-    P.n_rays = n_rays; P.cap = march_cap(scene); P.off3 = off3; P.dweight = dweight; P.dlast = dlast;
-    P.grad_sdf = grad_sdf;
-    return launch_march<MARCH_BWD, false, true>(P, esr_stream(stream));
-}
-
-// ---- coarse stage (VoxurfC): same march on the SMOOTHED sdf grid, two transmittance passes -------------
-ESR_API int esr_coarse_march_count(const esr_scene_t *scene, const float *rays_o, const float *rays_d,
-                                   const float *mask_density, const float *sdf_smooth, int32_t n_rays,
-                                   int32_t *cnt3, float *alphainv_last, float *cum_weights, int32_t *ray_stats,
-                                   esr_plan_t *plan, void *stream)
-{
-    if (!scene || n_rays < 0 || !plan) return ESR_EINVAL;
-    if (n_rays && (!rays_o || !rays_d || !mask_density || !sdf_smooth || !cnt3 || !alphainv_last || !cum_weights ||
-                   !ray_stats))
-        return ESR_EINVAL;
-    MarchParams P = {};
-    P.sc = *scene; P.rays_o = rays_o; P.rays_d = rays_d; P.mask_density = mask_density; P.sdf = sdf_smooth;
-    P.n_rays = n_rays; P.cap = march_cap(scene); P.cnt3 = cnt3; P.alphainv_last = alphainv_last;
-    P.cumw = cum_weights; P.stats = ray_stats; P.plan = plan;
-    return launch_march<MARCH_COUNT, true>(P, esr_stream(stream));
-}
-
-ESR_API int esr_coarse_march_fill(const esr_scene_t *scene, const float *rays_o, const float *rays_d,
-                                  const float *mask_density, const float *sdf_smooth, int32_t n_rays,
-                                  const int32_t *off3, int32_t *rec_ray, int32_t *rec_step, float *rec_w,
-                                  float *rec_sdf, void *stream)
-{
-    if (!scene || n_rays < 0) return ESR_EINVAL;
-    if (n_rays && (!rays_o || !rays_d || !mask_density || !sdf_smooth || !off3 || !rec_ray || !rec_step ||
-                   !rec_w || !rec_sdf))
-        return ESR_EINVAL;
-    MarchParams P = {};
-    P.sc = *scene; P.rays_o = rays_o; P.rays_d = rays_d; P.mask_density = mask_density; P.sdf = sdf_smooth;
-    P.n_rays = n_rays; P.cap = march_cap(scene); P.off3 = off3; P.rec_ray = rec_ray;
-    P.rec_step = rec_step; P.rec_w = rec_w; P.rec_sdf = rec_sdf;
-    return launch_march<MARCH_FILL, true>(P, esr_stream(stream));
-}
-
-ESR_API int esr_coarse_march_bwd(const esr_scene_t *scene, const float *rays_o, const float *rays_d,
-                                 const float *mask_density, const float *sdf_smooth, int32_t n_rays,
-                                 const int32_t *off3, const float *dweight, const float *dlast,
-                                 float *grad_sdf_smooth, void *stream)
-{
-    if (!scene || n_rays < 0) return ESR_EINVAL;
-    if (n_rays && (!rays_o || !rays_d || !mask_density || !sdf_smooth || !off3 || !dweight || !dlast ||
-                   !grad_sdf_smooth))
-        return ESR_EINVAL;
-    MarchParams P = {};
-    P.sc = *scene; P.rays_o = rays_o; P.rays_d = rays_d; P.mask_density = mask_density; P.sdf = sdf_smooth;
-    P.n_rays = n_rays; P.cap = march_cap(scene); P.off3 = off3; P.dweight = dweight; P.dlast = dlast;
-    P.grad_sdf = grad_sdf_smooth;
-    return launch_march<MARCH_BWD, true>(P, esr_stream(stream));
-}
-
-// ---- coarse stage with cfg neus_alpha: "grad" (voxurfc.py:171-174, 204-210): the section SDFs are extrapolated with the
-// trilinear sample of the dense gradient grid `gg` [X,Y,Z,3] (esr_central_grad_fwd of the UNSMOOTHED grid); the backward
-// adds d/d gg into grad_gg, which esr_central_grad_bwd folds into the SDF gradient ----
-ESR_API int esr_coarse_march_count_ga(const esr_scene_t *scene, const float *rays_o, const float *rays_d, const float *viewdirs,
-                                      const float *mask_density, const float *sdf_smooth, const float *gg, int32_t n_rays,
-                                      int32_t *cnt3, float *alphainv_last, float *cum_weights, int32_t *ray_stats,
-                                      esr_plan_t *plan, void *stream)
-{
-    if (!scene || n_rays < 0 || !plan) return ESR_EINVAL;
-    if (n_rays && (!rays_o || !rays_d || !viewdirs || !mask_density || !sdf_smooth || !gg || !cnt3 || !alphainv_last ||
-                   !cum_weights || !ray_stats))
-        return ESR_EINVAL;
-    MarchParams P = {};
-    P.sc = *scene; P.rays_o = rays_o; P.rays_d = rays_d; P.viewdirs = viewdirs; P.mask_density = mask_density;
-    P.sdf = sdf_smooth; P.gg = gg;
-    P.n_rays = n_rays; P.cap = march_cap(scene); P.cnt3 = cnt3; P.alphainv_last = alphainv_last;
-    P.cumw = cum_weights; P.stats = ray_stats; P.plan = plan;
-    return launch_march<MARCH_COUNT, true, true>(P, esr_stream(stream));
-}
-
-ESR_API int esr_coarse_march_fill_ga(const esr_scene_t *scene, const float *rays_o, const float *rays_d, const float *viewdirs,
-                                     const float *mask_density, const float *sdf_smooth, const float *gg, int32_t n_rays,
-                                     const int32_t *off3, int32_t *rec_ray, int32_t *rec_step, float *rec_w,
-                                     float *rec_sdf, void *stream)
-{
-    if (!scene || n_rays < 0) return ESR_EINVAL;
-    if (n_rays && (!rays_o || !rays_d || !viewdirs || !mask_density || !sdf_smooth || !gg || !off3 || !rec_ray ||
-                   !rec_step || !rec_w || !rec_sdf))
-        return ESR_EINVAL;
-    MarchParams P = {};
-    P.sc = *scene; P.rays_o = rays_o; P.rays_d = rays_d; P.viewdirs = viewdirs; P.mask_density = mask_density;
-    P.sdf = sdf_smooth; P.gg = gg;
-    P.n_rays = n_rays; P.cap = march_cap(scene); P.off3 = off3; P.rec_ray = rec_ray;
-    P.rec_step = rec_step; P.rec_w = rec_w; P.rec_sdf = rec_sdf;
-    return launch_march<MARCH_FILL, true, true>(P, esr_stream(stream));
-}
-
-ESR_API int esr_coarse_march_bwd_ga(const esr_scene_t *scene, const float *rays_o, const float *rays_d, const float *viewdirs,
-                                    const float *mask_density, const float *sdf_smooth, const float *gg, int32_t n_rays,
-                                    const int32_t *off3, const float *dweight, const float *dlast,
-                                    float *grad_sdf_smooth, float *grad_gg, void *stream)
-{
-    if (!scene || n_rays < 0) return ESR_EINVAL;
-    if (n_rays && (!rays_o || !rays_d || !viewdirs || !mask_density || !sdf_smooth || !gg || !off3 || !dweight || !dlast ||
-                   !grad_sdf_smooth || !grad_gg))
-        return ESR_EINVAL;
-    MarchParams P = {};
-    P.sc = *scene; P.rays_o = rays_o; P.rays_d = rays_d; P.viewdirs = viewdirs; P.mask_density = mask_density;
-    P.sdf = sdf_smooth; P.gg = gg;
-    P.n_rays = n_rays; P.cap = march_cap(scene); P.off3 = off3; P.dweight = dweight; P.dlast = dlast;
-    P.grad_sdf = grad_sdf_smooth; P.grad_gg = grad_gg;
-    return launch_march<MARCH_BWD, true, true>(P, esr_stream(stream));
-}
+ESR_API int esr_march_count(const esr_march_t *a, void *stream) { return march<MARCH_COUNT>(a, stream); }
+ESR_API int esr_march_fill(const esr_march_t *a, void *stream) { return march<MARCH_FILL>(a, stream); }
+ESR_API int esr_march_bwd(const esr_march_t *a, void *stream) { return march<MARCH_BWD>(a, stream); }

@@ -59,8 +59,8 @@ class March:
     """One march through ``FineEngine._march_plan``: what the fill, the feature kernels and the backward need from it."""
     scene: _lib.EsrScene
     variant: str                      # "cached" (one walk per step: the count pass records every mask-cache survivor, fill
-    #                                   copies, the backward starts at its scan) or "ga" (cfg neus_alpha "grad": the entry points
-    #                                   that take the rays' view directions; no cache: the gradient taps are not recorded)
+    #                                   copies, the backward starts at its scan) or "ga" (cfg neus_alpha "grad": the march reads
+    #                                   the rays' view directions; no cache: the gradient taps are not recorded)
     n: int
     rays_o: torch.Tensor
     rays_d: torch.Tensor
@@ -77,6 +77,17 @@ class March:
     counts: Dict[str, int] = None
     e_pre: object = None              # the side stream's event behind ``prelude()``: the main stream waits for it before the
     #                                   first consumer
+    args: _lib.EsrMarch = None        # the argument struct of esr_march_count / _fill / _bwd: the fields above once, here; each
+    #                                   pass adds its own.  It holds raw addresses: the fields above keep the tensors alive
+
+    def __post_init__(self):
+        p = _lib.ptr
+        self.args = _lib.EsrMarch(
+            scene=C.pointer(self.scene), rays_o=p(self.rays_o), rays_d=p(self.rays_d), mask_density=p(self.mask_density),
+            sdf=p(self.sdf), n_rays=self.n, cnt3=p(self.cnt3), off3=p(self.off3), ray_stats=p(self.stats),
+            alphainv_last=p(self.last), cache=p(self.cache))
+        if self.variant == "ga":
+            self.args.viewdirs, self.args.flags = p(self.viewdirs), _lib.MARCH_GRAD_ALPHA
 
 
 @dataclass
@@ -369,38 +380,21 @@ class FineEngine:
             out[name] = (n + 1, ms + e0.elapsed_time(e1))
         return out
 
-    # -- the march: one owner of the entry-point choice, one of the count -> plan -> fill protocol ------------------------------
-    def _march_launch(self, name, which, m: March, s, *tail, cached=True):
-        """THE place that picks a march entry point, for count, fill and backward alike.  ``tail``: the call's own arguments
-        behind the rays, the fields and ``n`` (count: the plan header; fill: the four record arrays; bwd: dweight, dlast,
-        grad_sdf[, dsdf, acc]).  ``cached=False``: a fresh walk although the march has a cache."""
-        L, p = self.L, _lib.ptr
-        sp, o, d = C.byref(m.scene), p(m.rays_o), p(m.rays_d)
-        if cached and m.variant == "cached":
-            if which == "count":
-                self._run(name, L.esr_fine_march_count_cached, sp, o, d, p(m.mask_density), p(m.sdf), m.n, p(m.cnt3), p(m.last),
-                          p(m.stats), *tail, p(m.cache), s)
-            elif which == "fill":
-                self._run(name, L.esr_fine_march_fill_cached, sp, o, d, m.n, p(m.off3), p(m.stats), p(m.cache), *tail, s)
-            else:
-                self._run(name, L.esr_fine_march_bwd_cached, sp, o, d, m.n, p(m.off3), p(m.stats), p(m.last), p(m.cache), *tail, s)
-            return
-        ga = m.variant == "ga"
-        rays = (sp, o, d, p(m.viewdirs)) if ga else (sp, o, d)
-        own = (p(m.cnt3), p(m.last), p(m.stats)) if which == "count" else (p(m.off3),)
-        self._run(name, getattr(L, f"esr_fine_march_{which}" + ("_ga" if ga else "")), *rays, p(m.mask_density), p(m.sdf), m.n,
-                  *own, *tail, s)
+    # -- the march: one argument struct per march (March.args), one owner of the count -> plan -> fill protocol ---------------
+    def _march_launch(self, name, which, m: March, s, **fields):
+        """Set the pass's own fields (tensors) of the march's argument struct and enqueue ``esr_march_<which>``."""
+        for k, t in fields.items():
+            setattr(m.args, k, _lib.ptr(t))
+        self._run(name, getattr(self.L, "esr_march_" + which), m.args, s)
 
     def _march_bwd(self, name, m: March, dweight, dlast, grad_sdf, dsdf, acc, s, walk=False):
         """Backward of one march.  Cached form: the value-tap gradients of the recorded samples go to ``dsdf`` (the
         feature backward folds them into its SDF window).  neus_alpha "grad", or ``walk``: a fresh walk that scatters every
         tap straight into ``grad_sdf`` (``dsdf`` is left untouched).  Returns whether ``dsdf`` was written."""
-        g = (_lib.ptr(dweight), _lib.ptr(dlast), _lib.ptr(grad_sdf))
-        if walk or m.variant != "cached":
-            self._march_launch(name, "bwd", m, s, *g, cached=False)
-            return False
-        self._march_launch(name, "bwd", m, s, *g, _lib.ptr(dsdf), acc)
-        return dsdf is not None
+        fold = m.variant == "cached" and not walk
+        m.args.cache, m.args.dsdf_rec, m.args.accumulate = (_lib.ptr(m.cache), _lib.ptr(dsdf), acc) if fold else (None, None, 0)
+        self._march_launch(name, "bwd", m, s, dweight=dweight, dlast=dlast, grad_sdf=grad_sdf)
+        return fold and dsdf is not None
 
     def _plan_header(self):
         """The plan header in pinned host memory (after the wait for its copy) -> (tiles_on, tiles_all, counts)."""
@@ -433,18 +427,17 @@ class FineEngine:
                 raise RuntimeError("neus_alpha='grad' marches need the rays' view directions")
             viewdirs = viewdirs.contiguous()
         rb = ws.ray_buf(n)
-        m = March(scene=scene, variant=variant, n=n, rays_o=rays_o, rays_d=rays_d, viewdirs=viewdirs, mask_density=mask_density,
-                  sdf=sdf, cnt3=rb["cnt3"], off3=rb["off3"], stats=rb["stats"],
-                  last=torch.empty(n, dtype=torch.float32, device=self.device))
         if variant == "cached":                 # sized by the scene's step bound, grow-only
             need = int(L.esr_fine_march_cache_floats(C.byref(scene), n))
             if ws.cache is None or ws.cache.numel() < need:
                 ws.cache = torch.empty(need, dtype=torch.float32, device=self.device)
-            m.cache = ws.cache
+        m = March(scene=scene, variant=variant, n=n, rays_o=rays_o, rays_d=rays_d, viewdirs=viewdirs, mask_density=mask_density,
+                  sdf=sdf, cnt3=rb["cnt3"], off3=rb["off3"], stats=rb["stats"],
+                  last=torch.empty(n, dtype=torch.float32, device=self.device), cache=ws.cache if variant == "cached" else None)
         if plan_dev is None:
             plan_dev = self.plan_dev
             self._run("plan_begin", L.esr_fine_plan_begin, _lib.ptr(plan_dev), s)
-        self._march_launch("march_count" + tag, "count", m, s, _lib.ptr(plan_dev))
+        self._march_launch("march_count" + tag, "count", m, s, plan=plan_dev)
         # the counts the host waits for first (a many-workgroup sum), their copy, THEN the one-workgroup scan of the offsets:
         # it runs while the host reads the header and enqueues (17 / 48 us off the path to the read-back)
         self._run("plan_totals", L.esr_fine_plan_totals, _lib.ptr(m.cnt3), _lib.ptr(em_modes), _lib.ptr(m.stats), n,
@@ -476,7 +469,7 @@ class FineEngine:
             if rec[0] is not pre_rec:                               # (the workspace grew: a new, unfilled buffer)
                 rec[0][: tiles * 32].fill_(-1)
             if m.tiles_all:
-                self._march_launch("march_fill" + tag, "fill", m, s, *[_lib.ptr(t) for t in rec])
+                self._march_launch("march_fill" + tag, "fill", m, s, rec_ray=rec[0], rec_step=rec[1], rec_w=rec[2], rec_sdf=rec[3])
         return m
 
     def pack(self, which: str, kind: int, weights: List[torch.Tensor], biases: List[torch.Tensor]):

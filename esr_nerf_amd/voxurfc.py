@@ -63,20 +63,21 @@ class CoarseEngine(FineEngine):
         srgb = torch.zeros(n, 3, dtype=torch.float32, device=dev)
         sp = C.byref(scene)
         self._run("plan_begin", L.esr_fine_plan_begin, _lib.ptr(self.plan_dev), s)
+        p = _lib.ptr
+        march = _lib.EsrMarch(scene=C.pointer(scene), rays_o=p(rays_o), rays_d=p(rays_d), mask_density=p(mask_density), sdf=p(sm),
+                              n_rays=n, flags=_lib.MARCH_COARSE, cnt3=p(cnt3), alphainv_last=p(last), cum_weights=p(cumw),
+                              ray_stats=p(stats), plan=p(self.plan_dev), off3=p(off3))
         if self.neus_grad:      # cfg neus_alpha: "grad": section SDFs extrapolated with the sampled gradient grid
-            self._run("march_count", L.esr_coarse_march_count_ga, sp, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(viewdirs),
-                      _lib.ptr(mask_density), _lib.ptr(sm), _lib.ptr(gg), n, _lib.ptr(cnt3), _lib.ptr(last), _lib.ptr(cumw),
-                      _lib.ptr(stats), _lib.ptr(self.plan_dev), s)
-        else:
-            self._run("march_count", L.esr_coarse_march_count, sp, _lib.ptr(rays_o), _lib.ptr(rays_d),
-                      _lib.ptr(mask_density), _lib.ptr(sm), n, _lib.ptr(cnt3), _lib.ptr(last), _lib.ptr(cumw),
-                      _lib.ptr(stats), _lib.ptr(self.plan_dev), s)
+            march.flags |= _lib.MARCH_GRAD_ALPHA
+            march.viewdirs, march.gg = p(viewdirs), p(gg)
+        self._run("march_count", L.esr_march_count, march, s)
         self._run("plan", L.esr_fine_plan, _lib.ptr(cnt3), _lib.ptr(em_modes), _lib.ptr(stats), n, _lib.ptr(off3),
                   _lib.ptr(self.plan_dev), s)
         self.plan_host.copy_(self.plan_dev, non_blocking=True)
         torch.cuda.current_stream(dev).synchronize()
         tiles_on, tiles_all, counts = self._plan_header()
-        ctx = dict(scene=scene, batch=batch, n=n, T=tiles_all, Ton=tiles_on, sm=sm, gg=gg, off3=off3, dims=dims,
+        # (march: the argument struct of the three march passes; it holds raw addresses, the entries beside it the tensors)
+        ctx = dict(scene=scene, batch=batch, n=n, T=tiles_all, Ton=tiles_on, sm=sm, gg=gg, off3=off3, dims=dims, march=march,
                    mask_density=mask_density, kernel_w=kernel_w, ksize=ksize, voxel=voxel_size, counts=counts)
         white_bg = (1.0 - cumw).unsqueeze(-1)
         if tiles_all == 0:
@@ -85,14 +86,8 @@ class CoarseEngine(FineEngine):
         b = self.ws
         T, Ton = tiles_all, tiles_on
         b["rec_ray"][: T * 32].fill_(-1)
-        if self.neus_grad:
-            self._run("march_fill", L.esr_coarse_march_fill_ga, sp, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(viewdirs),
-                      _lib.ptr(mask_density), _lib.ptr(sm), _lib.ptr(gg), n, _lib.ptr(off3), _lib.ptr(b["rec_ray"]),
-                      _lib.ptr(b["rec_step"]), _lib.ptr(b["rec_w"]), _lib.ptr(b["rec_sdf"]), s)
-        else:
-            self._run("march_fill", L.esr_coarse_march_fill, sp, _lib.ptr(rays_o), _lib.ptr(rays_d),
-                      _lib.ptr(mask_density), _lib.ptr(sm), n, _lib.ptr(off3), _lib.ptr(b["rec_ray"]),
-                      _lib.ptr(b["rec_step"]), _lib.ptr(b["rec_w"]), _lib.ptr(b["rec_sdf"]), s)
+        march.rec_ray, march.rec_step, march.rec_w, march.rec_sdf = p(b["rec_ray"]), p(b["rec_step"]), p(b["rec_w"]), p(b["rec_sdf"])
+        self._run("march_fill", L.esr_march_fill, march, s)
         self._run("feat_fwd", L.esr_coarse_feat_fwd, sp, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(viewdirs),
                   _lib.ptr(b["rec_ray"]), _lib.ptr(b["rec_step"]), Ton, T, _lib.ptr(gg), _lib.ptr(off_color),
                   _lib.ptr(emo_color), _lib.ptr(b["X"]), _lib.ptr(b["gnorm"]), s)
@@ -166,14 +161,11 @@ class CoarseEngine(FineEngine):
         else:
             dweight = z(32)
         # alphainv_last and the weights depend on the SMOOTHED grid; white_bg's dependence rides in dweight
+        march = ctx["march"]
+        march.dweight, march.dlast, march.grad_sdf = _lib.ptr(dweight), _lib.ptr(g_last), _lib.ptr(g_sm)
         if self.neus_grad:      # also adds d/d gradient-grid into g_gg (folded into the SDF gradient below)
-            self._run("march_bwd", L.esr_coarse_march_bwd_ga, sp, _lib.ptr(bt["rays_o"]), _lib.ptr(bt["rays_d"]),
-                      _lib.ptr(bt["viewdirs"]), _lib.ptr(ctx["mask_density"]), _lib.ptr(ctx["sm"]), _lib.ptr(ctx["gg"]), n,
-                      _lib.ptr(ctx["off3"]), _lib.ptr(dweight), _lib.ptr(g_last), _lib.ptr(g_sm), _lib.ptr(g_gg), s)
-        else:
-            self._run("march_bwd", L.esr_coarse_march_bwd, sp, _lib.ptr(bt["rays_o"]), _lib.ptr(bt["rays_d"]),
-                      _lib.ptr(ctx["mask_density"]), _lib.ptr(ctx["sm"]), n, _lib.ptr(ctx["off3"]), _lib.ptr(dweight),
-                      _lib.ptr(g_last), _lib.ptr(g_sm), s)
+            march.grad_gg = _lib.ptr(g_gg)
+        self._run("march_bwd", L.esr_march_bwd, march, s)
         self._run("gauss3d_bwd", L.esr_gauss3d_bwd, _lib.ptr(g_sm), ctx["kernel_w"], ctx["ksize"], *dims,
                   _lib.ptr(grads["sdf"]), s)
         self._run("central_grad_bwd", L.esr_central_grad_bwd, _lib.ptr(g_gg), *dims, C.c_float(ctx["voxel"]),

@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 32
+#define ESR_ABI_VERSION 33
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -192,18 +192,81 @@ typedef struct esr_plan {
 } esr_plan_t;
 
 /*
- * march, counting pass: per ray (one wavefront each) sampler -> mask cache ->
- * SDF tap -> NeuS-interp alpha -> alpha>thres -> transmittance with the early
- * stop -> weight>thres (voxurff.py:186-213, functions.py:72-105,
- * render_utils_kernel.cu:577-605).  mask_density [mx,my,mz] (max-pooled),
- * sdf [gx,gy,gz].  Writes cnt3 [n_rays] i32, alphainv_last [n_rays] f32 and ray_stats
- * [n_rays,3] i32 (in-box / mask-cache / alpha>thres survivors of the ray; esr_fine_plan sums
- * them into m0/m1/m2); sets plan->overflow (plan zeroed by esr_fine_plan_begin).
+ * The ray march: per ray (one wavefront each) sampler -> in-box -> mask cache -> SDF tap -> NeuS alpha -> alpha>thres ->
+ * transmittance with the early stop -> weight>thres (voxurff.py:186-213, functions.py:72-105,
+ * render_utils_kernel.cu:577-605), in three passes over ONE argument struct: esr_march_count (sizes), esr_fine_plan*
+ * (offsets, below), esr_march_fill (records), and esr_march_bwd.  A pass reads and writes only the fields listed for it
+ * (and for the variant `flags` / `cache` select); the others may stay set from another pass.  Variants:
+ *  - flags 0: the fine stage, NeuS "interp" alpha (section SDFs interpolated towards the surviving neighbours).
+ *  - ESR_MARCH_GRAD_ALPHA: cfg `neus_alpha: grad` (app/utils/base/functions.py:45-69): the section SDFs of a sample are
+ *    sdf -+ 0.5 * dist * (viewdirs[ray] . grad).  Fine stage: grad = the radius-1 clamped central differences of
+ *    sample_sdf_grad (app/fine/model/voxurff.py:670-721); the backward scatters through the value tap and the six gradient
+ *    taps.
+ *  - ESR_MARCH_COARSE: the coarse renderer (app/coarse/model/voxurfc.py:186-219): SDF tap of the SMOOTHED grid, NO alpha
+ *    threshold (plan.m2 == plan.m1), alpha2weight over ALL mask-cache survivors -> weight > thres -> alpha2weight AGAIN
+ *    over the survivors (weights, alphainv_last and cum_weights = sum of weights come from this second pass).  Same
+ *    protocol and record layout.
+ *  - both flags (voxurfc.py:171-174, 204-210): grad = the trilinear sample of the dense gradient grid `gg`
+ *    (esr_central_grad_fwd of the UNSMOOTHED SDF grid); the backward adds d/d gg into `grad_gg`, which
+ *    esr_central_grad_bwd folds into the SDF gradient.
+ *  - cache != NULL (flags 0 only): the three passes share a CACHE.  The count pass records, for every mask-cache survivor
+ *    of every ray, its SDF, step id, alpha, transmittance and survivor flags; the fill pass is then a plain copy of the
+ *    recorded samples and the backward starts at its reverse scan -- the walk (mask-cache and SDF fetch per step) and the
+ *    serial transmittance loop run once per step instead of three times.  Results are bit-identical to cache == NULL.
+ *    The cached fill and backward read ray_stats (both) and alphainv_last (backward) as the count pass left them, and
+ *    neither mask_density nor sdf.
+ * Return: ESR_EINVAL for a NULL struct / scene, n_rays < 0, a count without plan, unknown flag bits, cache or dsdf_rec
+ * together with a flag, gg or grad_gg without both flags, and (n_rays > 0) a NULL field the pass reads or writes;
+ * ESR_ECAP (nothing written) for a scene.max_steps whose backward does not fit the LDS; 0 without a launch for n_rays == 0.
  */
-int esr_fine_march_count(const esr_scene_t *scene, const float *rays_o, const float *rays_d,
-                         const float *mask_density, const float *sdf, int32_t n_rays,
-                         int32_t *cnt3, float *alphainv_last, int32_t *ray_stats, esr_plan_t *plan,
-                         void *stream);
+#define ESR_MARCH_COARSE 1
+#define ESR_MARCH_GRAD_ALPHA 2
+typedef struct esr_march {
+    const esr_scene_t *scene;                   /* [host]                                                            */
+    const float *rays_o, *rays_d;               /* [n_rays,3]                                                        */
+    const float *viewdirs;                      /* [n_rays,3] the batch's view directions; read only with
+                                                   ESR_MARCH_GRAD_ALPHA                                              */
+    const float *mask_density;                  /* [mx,my,mz] (max-pooled)                                           */
+    const float *sdf;                           /* [gx,gy,gz]; ESR_MARCH_COARSE: the SMOOTHED grid                   */
+    const float *gg;                            /* both flags: gradient grid [gx,gy,gz,3], else NULL                 */
+    int32_t n_rays;
+    int32_t flags;                              /* ESR_MARCH_COARSE | ESR_MARCH_GRAD_ALPHA                           */
+    /* count writes (cached fill / backward read ray_stats, cached backward alphainv_last) */
+    int32_t *cnt3;                              /* [n_rays] survivors of the ray                                     */
+    float *alphainv_last;                       /* [n_rays]                                                          */
+    float *cum_weights;                         /* [n_rays], ESR_MARCH_COARSE only (white_bg = 1 - cum_weights)      */
+    int32_t *ray_stats;                         /* [n_rays,3] in-box / mask-cache / alpha>thres survivors of the ray;
+                                                   esr_fine_plan sums them into m0/m1/m2                             */
+    esr_plan_t *plan;                           /* count sets plan->overflow (zeroed by esr_fine_plan_begin)         */
+    /* fill and backward read; fill writes one record per surviving sample at off3[ray] + rank */
+    const int32_t *off3;                        /* [n_rays] (esr_fine_plan)                                          */
+    int32_t *rec_ray, *rec_step;                /* [n_tiles*32]; padding entries must have been set to rec_ray = -1
+                                                   by the caller                                                     */
+    float *rec_w, *rec_sdf;                     /* [n_tiles*32]                                                      */
+    /* backward */
+    const float *dweight;                       /* [n_tiles*32] d(weights), indexed like the records                 */
+    const float *dlast;                         /* [n_rays] d(alphainv_last)                                         */
+    float *grad_sdf;                            /* [gx,gy,gz] atomic scatter through the compositing scan, the alpha
+                                                   formula and the trilinear tap(s); ESR_MARCH_COARSE: of the SMOOTHED
+                                                   grid                                                              */
+    float *grad_gg;                             /* both flags: [gx,gy,gz,3], added to (zero-initialised or already
+                                                   holding the normal features' share), else NULL                    */
+    float *dsdf_rec;                            /* optional, flags 0: the value-tap gradient of every RECORDED sample
+                                                   (the ones esr_march_fill wrote) goes to dsdf_rec [n_tiles*32]
+                                                   (indexed like the records) instead of being scattered: pass that
+                                                   array as `dsdf_extra` to esr_fine_feat_bwd, which folds it into the
+                                                   SDF window it builds anyway (no L2 atomics for it).  Samples that
+                                                   were walked but not recorded (below a threshold, yet neighbours of a
+                                                   recorded one) are still scattered into grad_sdf                   */
+    int32_t accumulate;                         /* 0: every recorded slot of dsdf_rec is overwritten (padding slots are
+                                                   left alone; the feature backward never reads them); 1: added to
+                                                   what the caller put there                                         */
+    float *cache;                               /* NULL or esr_fine_march_cache_floats(scene, n_rays) floats         */
+} esr_march_t;
+int64_t esr_fine_march_cache_floats(const esr_scene_t *scene, int32_t n_rays);
+int esr_march_count(const esr_march_t *a, void *stream);
+int esr_march_fill(const esr_march_t *a, void *stream);
+int esr_march_bwd(const esr_march_t *a, void *stream);
 
 int esr_fine_plan_begin(esr_plan_t *plan, void *stream);
 
@@ -225,74 +288,6 @@ int esr_fine_plan_totals(const int32_t *cnt3, const int64_t *em_modes, const int
                          esr_plan_t *plan, void *stream);
 int esr_fine_plan_offsets(const int32_t *cnt3, const int64_t *em_modes, int32_t n_rays, int32_t *off3, esr_plan_t *plan,
                           void *stream);
-
-/*
- * march, fill pass: recomputes the march and writes one record per surviving
- * sample at off3[ray] + rank: rec_ray, rec_step (i32), rec_w, rec_sdf (f32).
- * Padding entries must have been set to rec_ray = -1 by the caller.
- */
-int esr_fine_march_fill(const esr_scene_t *scene, const float *rays_o, const float *rays_d,
-                        const float *mask_density, const float *sdf, int32_t n_rays,
-                        const int32_t *off3, int32_t *rec_ray, int32_t *rec_step,
-                        float *rec_w, float *rec_sdf, void *stream);
-
-/*
- * march backward: d(weights), d(alphainv_last) -> atomic scatter into grad_sdf
- * [gx,gy,gz] through the compositing scan, the alpha formula and the trilinear
- * tap.  dweight [n_tiles*32] is indexed like the records.
- */
-int esr_fine_march_bwd(const esr_scene_t *scene, const float *rays_o, const float *rays_d,
-                       const float *mask_density, const float *sdf, int32_t n_rays,
-                       const int32_t *off3, const float *dweight, const float *dlast,
-                       float *grad_sdf, void *stream);
-
-/*
- * As esr_fine_march_bwd, but the value-tap gradient of every RECORDED sample (the ones esr_fine_march_fill wrote) is
- * added to dsdf_rec [n_tiles*32] (indexed like the records) instead of being scattered: pass that array as
- * `dsdf_extra` to esr_fine_feat_bwd, which folds it into the SDF window it builds anyway (no L2 atomics for it).
- * Samples that were walked but not recorded (below a threshold, yet neighbours of a recorded one) are still scattered
- * into grad_sdf.  accumulate = 0: every recorded slot of dsdf_rec is overwritten (padding slots are left alone; the
- * feature backward never reads them); accumulate = 1: added to what the caller put there.
- */
-int esr_fine_march_bwd_rec(const esr_scene_t *scene, const float *rays_o, const float *rays_d,
-                           const float *mask_density, const float *sdf, int32_t n_rays,
-                           const int32_t *off3, const float *dweight, const float *dlast,
-                           float *grad_sdf, float *dsdf_rec, int32_t accumulate, void *stream);
-
-/*
- * The three passes with a shared CACHE: the count pass records, for every mask-cache survivor of every ray, its SDF,
- * step id, alpha, transmittance and survivor flags (cache: esr_fine_march_cache_floats(scene, n_rays) floats); the fill
- * pass is then a plain copy of the recorded samples and the backward starts at its reverse scan -- the walk (mask-cache
- * and SDF fetch per step) and the serial transmittance loop run once per step instead of three times.  Results are
- * bit-identical to the uncached entry points.  ray_stats / alphainv_last: the count pass's outputs, untouched since.
- */
-int64_t esr_fine_march_cache_floats(const esr_scene_t *scene, int32_t n_rays);
-int esr_fine_march_count_cached(const esr_scene_t *scene, const float *rays_o, const float *rays_d,
-                                const float *mask_density, const float *sdf, int32_t n_rays, int32_t *cnt3,
-                                float *alphainv_last, int32_t *ray_stats, esr_plan_t *plan, float *cache, void *stream);
-int esr_fine_march_fill_cached(const esr_scene_t *scene, const float *rays_o, const float *rays_d, int32_t n_rays,
-                               const int32_t *off3, const int32_t *ray_stats, const float *cache,
-                               int32_t *rec_ray, int32_t *rec_step, float *rec_w, float *rec_sdf, void *stream);
-int esr_fine_march_bwd_cached(const esr_scene_t *scene, const float *rays_o, const float *rays_d, int32_t n_rays,
-                              const int32_t *off3, const int32_t *ray_stats, const float *alphainv_last,
-                              const float *cache, const float *dweight, const float *dlast, float *grad_sdf,
-                              float *dsdf_rec, int32_t accumulate, void *stream);
-
-/*
- * The same three march entry points for cfg `neus_alpha: grad` (app/utils/base/functions.py:45-69): the section
- * SDFs of a sample are sdf -+ 0.5 * dist * (viewdirs[ray] . grad) with grad = the radius-1 clamped central
- * differences of sample_sdf_grad (app/fine/model/voxurff.py:670-721); `viewdirs` [n_rays,3] is the batch's
- * view-direction tensor.  The backward scatters through the value tap and the six gradient taps.
- */
-int esr_fine_march_count_ga(const esr_scene_t *scene, const float *rays_o, const float *rays_d, const float *viewdirs,
-                            const float *mask_density, const float *sdf, int32_t n_rays, int32_t *cnt3,
-                            float *alphainv_last, int32_t *ray_stats, esr_plan_t *plan, void *stream);
-int esr_fine_march_fill_ga(const esr_scene_t *scene, const float *rays_o, const float *rays_d, const float *viewdirs,
-                           const float *mask_density, const float *sdf, int32_t n_rays, const int32_t *off3,
-                           int32_t *rec_ray, int32_t *rec_step, float *rec_w, float *rec_sdf, void *stream);
-int esr_fine_march_bwd_ga(const esr_scene_t *scene, const float *rays_o, const float *rays_d, const float *viewdirs,
-                          const float *mask_density, const float *sdf, int32_t n_rays, const int32_t *off3,
-                          const float *dweight, const float *dlast, float *grad_sdf, void *stream);
 
 /*
  * Per-sample feature assembly (voxurff.py:219-254 + :678-721 + module.py:24-35; the LTS renderer's
@@ -844,46 +839,6 @@ int esr_central_grad_bwd(const float *ggrad, int32_t gx, int32_t gy, int32_t gz,
                          float *gsdf, void *stream);
 
 /*
- * Fused march of the coarse renderer (app/coarse/model/voxurfc.py:186-219): sampler -> in-box ->
- * mask cache -> SDF tap of the SMOOTHED grid -> NeuS "interp" alpha -> alpha2weight over ALL
- * mask-cache survivors -> weight > thres -> alpha2weight AGAIN over the survivors (weights,
- * alphainv_last and cum_weights = sum of weights come from this second pass).  Same three-call
- * protocol and record layout as esr_fine_march_*; plan.m2 == plan.m1 (there is no alpha mask).
- */
-int esr_coarse_march_count(const esr_scene_t *scene, const float *rays_o, const float *rays_d,
-                           const float *mask_density, const float *sdf_smooth, int32_t n_rays,
-                           int32_t *cnt3, float *alphainv_last, float *cum_weights, int32_t *ray_stats,
-                           esr_plan_t *plan, void *stream);
-int esr_coarse_march_fill(const esr_scene_t *scene, const float *rays_o, const float *rays_d,
-                          const float *mask_density, const float *sdf_smooth, int32_t n_rays,
-                          const int32_t *off3, int32_t *rec_ray, int32_t *rec_step, float *rec_w,
-                          float *rec_sdf, void *stream);
-int esr_coarse_march_bwd(const esr_scene_t *scene, const float *rays_o, const float *rays_d,
-                         const float *mask_density, const float *sdf_smooth, int32_t n_rays,
-                         const int32_t *off3, const float *dweight, const float *dlast,
-                         float *grad_sdf_smooth, void *stream);
-
-/*
- * The coarse march under cfg neus_alpha: "grad" (app/coarse/model/voxurfc.py:171-174, 204-210;
- * app/utils/base/functions.py:45-69): section SDFs extrapolated with the trilinear sample of the dense gradient grid
- * gg [X,Y,Z,3] (esr_central_grad_fwd of the unsmoothed SDF grid) along the batch's view directions.  The backward adds
- * d/d gg into grad_gg [X,Y,Z,3] (zero-initialised or already holding the normal features' share), which
- * esr_central_grad_bwd folds into the SDF gradient.
- */
-int esr_coarse_march_count_ga(const esr_scene_t *scene, const float *rays_o, const float *rays_d, const float *viewdirs,
-                              const float *mask_density, const float *sdf_smooth, const float *gg, int32_t n_rays,
-                              int32_t *cnt3, float *alphainv_last, float *cum_weights, int32_t *ray_stats,
-                              esr_plan_t *plan, void *stream);
-int esr_coarse_march_fill_ga(const esr_scene_t *scene, const float *rays_o, const float *rays_d, const float *viewdirs,
-                             const float *mask_density, const float *sdf_smooth, const float *gg, int32_t n_rays,
-                             const int32_t *off3, int32_t *rec_ray, int32_t *rec_step, float *rec_w, float *rec_sdf,
-                             void *stream);
-int esr_coarse_march_bwd_ga(const esr_scene_t *scene, const float *rays_o, const float *rays_d, const float *viewdirs,
-                            const float *mask_density, const float *sdf_smooth, const float *gg, int32_t n_rays,
-                            const int32_t *off3, const float *dweight, const float *dlast, float *grad_sdf_smooth,
-                            float *grad_gg, void *stream);
-
-/*
  * Per-sample features of the coarse renderer (app/coarse/model/voxurfc.py:221-250) on the march
  * records.  grad_grid [gx,gy,gz,3] (esr_central_grad_fwd), off_color / emo_color [gx,gy,gz,12]
  * channels-last.  X [tiles,72,32] rows: 0-11 off colour | 12-23 emo colour (on-tiles) | 24-26 normal
@@ -1288,7 +1243,7 @@ int esr_edit_label(const float *esp, int64_t n, const float *w2c, float focal, i
  * scene: xyz_min / xyz_max, mask_min / mask_max, mx / my / mz, near_, stepdist (= stepsize * voxel_size in f32), act_shift
  * and mask_thres are read.  mask_density [mx,my,mz] f32 (max-pooled), rays_o / rays_d [n_rays,3] f32.
  * mode ESR_RAY_FILTER_MARCH: every step 0 .. n_steps - 1 of the march sampler with far = 1e9 (far_ and n_samples are not
- * read); there is NO per-ray step cap (unlike esr_fine_march_count's scene.max_steps).  mode ESR_RAY_FILTER_FIXED: far_ =
+ * read); there is NO per-ray step cap (unlike esr_march_count's scene.max_steps).  mode ESR_RAY_FILTER_FIXED: far_ =
  * the model's far, n_samples [host] = int(|grid_shape + 1| / stepsize) + 1; a ray with t_max <= t_min is dropped.
  * keep u8 [n_rays]; first_hit (or NULL) i32 [n_rays]: the index of the first kept step, -1 for a dropped ray.
  * n_rays == 0 launches nothing.  One wave per ray, no atomics, no workspace: the same bytes on every call.  Arithmetic

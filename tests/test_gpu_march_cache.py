@@ -1,5 +1,5 @@
-"""The three march passes with a shared cache (esr_fine_march_*_cached: one walk per step) against the uncached entry
-points on the same rays: records bit-identical, SDF gradient equal up to the summation order of float atomics, and the
+"""The three march passes with a shared cache (esr_march_t.cache: one walk per step) against the uncached passes
+on the same rays: records bit-identical, SDF gradient equal up to the summation order of float atomics, and the
 per-record value-tap array (dsdf_rec) + direct scatter equal to the uncached backward's scatter."""
 import ctypes as C
 
@@ -34,40 +34,25 @@ def test_cached_march_equals_uncached(mask, s_val, oblique):
         cnt3, off3, stats, last = i32(n), i32(n), i32(3 * n), torch.empty(n, device=dev)
         plan = torch.zeros(8, dtype=torch.int32, device=dev)
         cache = torch.empty(int(L.esr_fine_march_cache_floats(sp, n)), device=dev) if cached else None
-        if cached:
-            _lib.check(L.esr_fine_march_count_cached(sp, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(mask_d), _lib.ptr(sdf), n,
-                                                     _lib.ptr(cnt3), _lib.ptr(last), _lib.ptr(stats), _lib.ptr(plan),
-                                                     _lib.ptr(cache), s), "count_cached")
-        else:
-            _lib.check(L.esr_fine_march_count(sp, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(mask_d), _lib.ptr(sdf), n,
-                                              _lib.ptr(cnt3), _lib.ptr(last), _lib.ptr(stats), _lib.ptr(plan), s), "count")
+        p = _lib.ptr
+        ma = _lib.EsrMarch(scene=C.pointer(scene), rays_o=p(rays_o), rays_d=p(rays_d), mask_density=p(mask_d), sdf=p(sdf), n_rays=n,
+                           cnt3=p(cnt3), alphainv_last=p(last), ray_stats=p(stats), plan=p(plan), off3=p(off3), cache=p(cache))
+        _lib.check(L.esr_march_count(ma, s), "count_cached" if cached else "count")
         _lib.check(L.esr_fine_plan(_lib.ptr(cnt3), _lib.ptr(em), _lib.ptr(stats), n, _lib.ptr(off3), _lib.ptr(plan), s), "plan")
         hdr = plan.tolist()
         tiles = hdr[3]
         assert tiles > 0 and hdr[7] == 0
         rec_ray = torch.full((tiles * 32,), -1, dtype=torch.int32, device=dev)
         rec_step, rec_w, rec_sdf = i32(tiles * 32).zero_(), torch.zeros(tiles * 32, device=dev), torch.zeros(tiles * 32, device=dev)
-        if cached:
-            _lib.check(L.esr_fine_march_fill_cached(sp, _lib.ptr(rays_o), _lib.ptr(rays_d), n, _lib.ptr(off3), _lib.ptr(stats),
-                                                    _lib.ptr(cache), _lib.ptr(rec_ray), _lib.ptr(rec_step), _lib.ptr(rec_w),
-                                                    _lib.ptr(rec_sdf), s), "fill_cached")
-        else:
-            _lib.check(L.esr_fine_march_fill(sp, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(mask_d), _lib.ptr(sdf), n,
-                                             _lib.ptr(off3), _lib.ptr(rec_ray), _lib.ptr(rec_step), _lib.ptr(rec_w),
-                                             _lib.ptr(rec_sdf), s), "fill")
+        ma.rec_ray, ma.rec_step, ma.rec_w, ma.rec_sdf = p(rec_ray), p(rec_step), p(rec_w), p(rec_sdf)
+        _lib.check(L.esr_march_fill(ma, s), "fill_cached" if cached else "fill")
         g = torch.Generator(device="cpu").manual_seed(7)
         dweight = torch.randn(tiles * 32, generator=g).to(dev)
         dlast = torch.randn(n, generator=g).to(dev)
         grad = torch.zeros_like(sdf)
         dsdf = torch.zeros(tiles * 32, device=dev)
-        if cached:
-            _lib.check(L.esr_fine_march_bwd_cached(sp, _lib.ptr(rays_o), _lib.ptr(rays_d), n, _lib.ptr(off3), _lib.ptr(stats),
-                                                   _lib.ptr(last), _lib.ptr(cache), _lib.ptr(dweight), _lib.ptr(dlast),
-                                                   _lib.ptr(grad), _lib.ptr(dsdf), 0, s), "bwd_cached")
-        else:
-            _lib.check(L.esr_fine_march_bwd_rec(sp, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(mask_d), _lib.ptr(sdf), n,
-                                                _lib.ptr(off3), _lib.ptr(dweight), _lib.ptr(dlast), _lib.ptr(grad),
-                                                _lib.ptr(dsdf), 0, s), "bwd_rec")
+        ma.dweight, ma.dlast, ma.grad_sdf, ma.dsdf_rec, ma.accumulate = p(dweight), p(dlast), p(grad), p(dsdf), 0
+        _lib.check(L.esr_march_bwd(ma, s), "bwd_cached" if cached else "bwd_rec")
         torch.cuda.synchronize()
         out[cached] = dict(cnt3=cnt3, off3=off3, stats=stats, last=last, hdr=hdr, rec_ray=rec_ray, rec_step=rec_step,
                            rec_w=rec_w, rec_sdf=rec_sdf, grad=grad, dsdf=dsdf)

@@ -143,31 +143,31 @@ class Run:
     def p(self, t):
         return self.lib.ptr(t)
 
+    def args(self, **own):
+        """The argument struct of the three passes for this (coarse, ga) with the pass's ``own`` fields (tensors, or ints)."""
+        lib, p = self.lib, self.p
+        a = lib.EsrMarch(scene=C.pointer(self.sc.struct()), rays_o=p(self.o), rays_d=p(self.d), mask_density=p(self.mask),
+                         sdf=p(self.sdf), n_rays=self.n,
+                         flags=(lib.MARCH_COARSE if self.coarse else 0) | (lib.MARCH_GRAD_ALPHA if self.ga else 0))
+        if self.ga:
+            a.viewdirs = p(self.vd)
+        if self.coarse and self.ga:
+            a.gg = p(self.gg)
+        for k, v in own.items():
+            setattr(a, k, v if isinstance(v, int) else p(v))
+        return a
+
     def count(self, cached=False, expect=0):
-        n, p, L, sp = self.n, self.p, self.L, C.byref(self.sc.struct())
+        n, L, sp = self.n, self.L, C.byref(self.sc.struct())
         i32 = lambda k: torch.full((k,), -7, dtype=torch.int32, device=DEV)
         out = dict(cnt3=i32(n), stats=i32(3 * n), last=torch.full((n,), -7.0, device=DEV),
                    cumw=torch.full((n,), -7.0, device=DEV), plan=torch.zeros(8, dtype=torch.int32, device=DEV))
-        cache = None
+        own = dict(cnt3=out["cnt3"], alphainv_last=out["last"], ray_stats=out["stats"], plan=out["plan"])
+        if self.coarse:
+            own["cum_weights"] = out["cumw"]
         if cached:
-            cache = torch.full((int(L.esr_fine_march_cache_floats(sp, n)),), -7.0, device=DEV)
-            out["cache"] = cache
-        a = (p(out["cnt3"]), p(out["last"]))
-        if self.coarse and self.ga:
-            rc = L.esr_coarse_march_count_ga(sp, p(self.o), p(self.d), p(self.vd), p(self.mask), p(self.sdf), p(self.gg), n, *a,
-                                             p(out["cumw"]), p(out["stats"]), p(out["plan"]), self.s)
-        elif self.coarse:
-            rc = L.esr_coarse_march_count(sp, p(self.o), p(self.d), p(self.mask), p(self.sdf), n, *a, p(out["cumw"]),
-                                          p(out["stats"]), p(out["plan"]), self.s)
-        elif self.ga:
-            rc = L.esr_fine_march_count_ga(sp, p(self.o), p(self.d), p(self.vd), p(self.mask), p(self.sdf), n, *a,
-                                           p(out["stats"]), p(out["plan"]), self.s)
-        elif cached:
-            rc = L.esr_fine_march_count_cached(sp, p(self.o), p(self.d), p(self.mask), p(self.sdf), n, *a, p(out["stats"]),
-                                               p(out["plan"]), p(cache), self.s)
-        else:
-            rc = L.esr_fine_march_count(sp, p(self.o), p(self.d), p(self.mask), p(self.sdf), n, *a, p(out["stats"]),
-                                        p(out["plan"]), self.s)
+            out["cache"] = own["cache"] = torch.full((int(L.esr_fine_march_cache_floats(sp, n)),), -7.0, device=DEV)
+        rc = L.esr_march_count(self.args(**own), self.s)
         assert rc == expect, rc
         torch.cuda.synchronize()
         return {k: v.cpu() for k, v in out.items()}
@@ -182,52 +182,28 @@ class Run:
         return off3.cpu(), plan.cpu().tolist()
 
     def fill(self, off3, tiles, cached=None, expect=0):
-        n, p, L, sp = self.n, self.p, self.L, C.byref(self.sc.struct())
         m = max(tiles, 1) * 32
         out = dict(ray=torch.full((m,), -1, dtype=torch.int32, device=DEV), step=torch.full((m,), -7, dtype=torch.int32, device=DEV),
                    w=torch.full((m,), -7.0, device=DEV), sdf=torch.full((m,), -7.0, device=DEV))
-        o3 = _dev(off3)
-        r = (p(out["ray"]), p(out["step"]), p(out["w"]), p(out["sdf"]))
+        own = dict(off3=_dev(off3), rec_ray=out["ray"], rec_step=out["step"], rec_w=out["w"], rec_sdf=out["sdf"])
         if cached is not None:
-            st, ca = _dev(cached["stats"]), _dev(cached["cache"])
-            rc = L.esr_fine_march_fill_cached(sp, p(self.o), p(self.d), n, p(o3), p(st), p(ca), *r, self.s)
-        elif self.coarse and self.ga:
-            rc = L.esr_coarse_march_fill_ga(sp, p(self.o), p(self.d), p(self.vd), p(self.mask), p(self.sdf), p(self.gg), n, p(o3),
-                                            *r, self.s)
-        elif self.coarse:
-            rc = L.esr_coarse_march_fill(sp, p(self.o), p(self.d), p(self.mask), p(self.sdf), n, p(o3), *r, self.s)
-        elif self.ga:
-            rc = L.esr_fine_march_fill_ga(sp, p(self.o), p(self.d), p(self.vd), p(self.mask), p(self.sdf), n, p(o3), *r, self.s)
-        else:
-            rc = L.esr_fine_march_fill(sp, p(self.o), p(self.d), p(self.mask), p(self.sdf), n, p(o3), *r, self.s)
+            own.update(ray_stats=_dev(cached["stats"]), cache=_dev(cached["cache"]))
+        rc = self.L.esr_march_fill(self.args(**own), self.s)
         assert rc == expect, rc
         torch.cuda.synchronize()
         return {k: v.cpu() for k, v in out.items()}
 
     def bwd(self, off3, dweight, dlast, rec=None, acc=0, cached=None, prefill=None, expect=0):
         """rec: None (plain) or a prefilled dsdf_rec array; cached: the cached COUNT's outputs."""
-        n, p, L, sp = self.n, self.p, self.L, C.byref(self.sc.struct())
         grad = torch.zeros(self.sdf.shape, device=DEV)
         ggrad = torch.zeros(self.gg.shape, device=DEV)
         dsdf = _dev(rec) if rec is not None else None
-        o3, dw, dl = _dev(off3), _dev(dweight), _dev(dlast)
+        own = dict(off3=_dev(off3), dweight=_dev(dweight), dlast=_dev(dlast), grad_sdf=grad, dsdf_rec=dsdf, accumulate=acc)
+        if self.coarse and self.ga:
+            own["grad_gg"] = ggrad
         if cached is not None:
-            st, la, ca = _dev(cached["stats"]), _dev(cached["last"]), _dev(cached["cache"])
-            rc = L.esr_fine_march_bwd_cached(sp, p(self.o), p(self.d), n, p(o3), p(st), p(la), p(ca), p(dw), p(dl), p(grad),
-                                             p(dsdf), acc, self.s)
-        elif self.coarse and self.ga:
-            rc = L.esr_coarse_march_bwd_ga(sp, p(self.o), p(self.d), p(self.vd), p(self.mask), p(self.sdf), p(self.gg), n, p(o3),
-                                           p(dw), p(dl), p(grad), p(ggrad), self.s)
-        elif self.coarse:
-            rc = L.esr_coarse_march_bwd(sp, p(self.o), p(self.d), p(self.mask), p(self.sdf), n, p(o3), p(dw), p(dl), p(grad), self.s)
-        elif self.ga:
-            rc = L.esr_fine_march_bwd_ga(sp, p(self.o), p(self.d), p(self.vd), p(self.mask), p(self.sdf), n, p(o3), p(dw), p(dl),
-                                         p(grad), self.s)
-        elif rec is not None:
-            rc = L.esr_fine_march_bwd_rec(sp, p(self.o), p(self.d), p(self.mask), p(self.sdf), n, p(o3), p(dw), p(dl), p(grad),
-                                          p(dsdf), acc, self.s)
-        else:
-            rc = L.esr_fine_march_bwd(sp, p(self.o), p(self.d), p(self.mask), p(self.sdf), n, p(o3), p(dw), p(dl), p(grad), self.s)
+            own.update(ray_stats=_dev(cached["stats"]), alphainv_last=_dev(cached["last"]), cache=_dev(cached["cache"]))
+        rc = self.L.esr_march_bwd(self.args(**own), self.s)
         assert rc == expect, rc
         torch.cuda.synchronize()
         return grad.cpu(), ggrad.cpu(), None if dsdf is None else dsdf.cpu()
