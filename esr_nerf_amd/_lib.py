@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libesr_hip.so")
 # developer experiments only (python -m esr_nerf_amd.build --variant builds alternative libraries; tools/ab_env.sh times them
 # side by side on one box)
 LIB_PATH = os.environ.get("ESR_LIB_PATH", LIB_PATH)
-ABI_VERSION = 33
+ABI_VERSION = 34
 _lib = None
 
 
@@ -136,6 +136,8 @@ class EsrCamera(C.Structure):           # esr_camera_t
 
 CAMERA_LDS_VIEWS = 256                  # ESR_CAMERA_LDS_VIEWS
 CAMERA_BOUNDS_BLOCKS = 1024             # ESR_CAMERA_BOUNDS_BLOCKS
+RESAMPLE_MAX_C = 16                     # ESR_RESAMPLE_MAX_C
+DENSITY_BOUNDS_BLOCKS = 1024            # ESR_DENSITY_BOUNDS_BLOCKS
 
 
 class EsrMlpWeights(C.Structure):
@@ -183,6 +185,7 @@ EXPORTS = [
     "esr_ray_filter",
     "esr_adam_step_live", "esr_brick_live_from_moments",
     "esr_camera_rays", "esr_camera_batch", "esr_camera_bounds", "esr_ray_filter_cameras",
+    "esr_grid_resample", "esr_maxpool3d", "esr_nonempty_mask", "esr_density_bounds",
 ]
 
 # full ctypes signatures (argument conversion checked on every call) of the entries that declare them
@@ -206,6 +209,14 @@ SIGNATURES = {
     "esr_camera_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "esr_ray_filter_cameras": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32,
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esr_grid_resample": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_void_p]),
+    "esr_maxpool3d": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "esr_nonempty_mask": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_float, C.c_float,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esr_density_bounds": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_float, C.c_float,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

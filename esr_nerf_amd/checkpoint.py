@@ -84,11 +84,72 @@ def fine_from_coarse(cls, cfg, coarse_rec: Dict[str, Any], device, num_voxels: i
     nv = int(num_voxels / (scale_ratio ** len(pg_scale))) if len(pg_scale) else num_voxels
     renderer = build_renderer(cls, cfg, coarse_rec, device, num_voxels=nv, load_params=False)
     sdf = coarse_rec["params"]["sdf.grid"].to(device) / sdf_reduce
-    if sdf.shape != renderer.sdf.grid.shape:
-        sdf = F.interpolate(sdf, size=tuple(int(v) for v in renderer.world_size), mode="trilinear", align_corners=True)
-    smooth = Gaussian3DConv(ksize=5, sigma=1).to(device)
-    with torch.no_grad():
-        renderer.sdf.grid.copy_(smooth(sdf))
+    smooth = Gaussian3DConv(ksize=5, sigma=1)
+    if renderer.sdf.grid.is_cuda:
+        # the division above stays a torch op on the coarse grid (reference order, fine.py:163); resample and smoothing in HIP
+        import ctypes as C
+        from . import _lib
+        from .gridsetup import resample_grid
+        size = tuple(int(v) for v in renderer.world_size)
+        vol = sdf.contiguous().view(*sdf.shape[2:])
+        if sdf.shape != renderer.sdf.grid.shape:
+            vol = resample_grid(vol, size)
+        w = (C.c_float * 125)(*smooth.m.weight.detach().flatten().tolist())
+        dev = vol.device
+        with torch.no_grad(), torch.cuda.device(dev):
+            _lib.check(_lib.lib().esr_gauss3d_fwd(_lib.ptr(vol), w, 5, *size, _lib.ptr(renderer.sdf.grid.data),
+                                                  _lib.stream_ptr(dev)), "esr_gauss3d_fwd")
+    else:
+        if sdf.shape != renderer.sdf.grid.shape:
+            sdf = F.interpolate(sdf, size=tuple(int(v) for v in renderer.world_size), mode="trilinear", align_corners=True)
+        smooth = smooth.to(device)
+        with torch.no_grad():
+            renderer.sdf.grid.copy_(smooth(sdf))
     renderer.set_nonempty_mask()
     renderer.sdf_random_init = False
     return renderer
+
+
+def alphamask_bounds(density: torch.Tensor, xyz_min: torch.Tensor, xyz_max: torch.Tensor, alpha_init: float,
+                     bbox_thres: float):
+    """``(xyz_min, xyz_max)`` of the alphamask density's nodes whose alpha exceeds ``bbox_thres``
+    (compute_bbox_by_coarse_geo, coarse.py:152-182).  A density on the GPU runs ``gridsetup.density_bounds``; a CPU-resident
+    one the torch lines below."""
+    import math
+    act_shift = math.log(1 / (1 - alpha_init) - 1)                   # DVGO.act_shift (dvgo.py:37)
+    if density.is_cuda:
+        from .gridsetup import density_bounds
+        return density_bounds(density, (xyz_min, xyz_max), act_shift, bbox_thres)
+    return _alphamask_bounds_torch(density, xyz_min, xyz_max, act_shift, bbox_thres)
+
+
+def _alphamask_bounds_torch(density, xyz_min, xyz_max, act_shift: float, bbox_thres: float):
+    """The torch body of ``alphamask_bounds`` (CPU-resident densities; tools/stage_setup_time.py times it against the
+    kernel): coarse.py:154-174 with DVGO.grid_sampler and DVGO.activate_density written out."""
+    from .gridsetup import bounds_axes
+    lo, hi = xyz_min.float().to(density.device), xyz_max.float().to(density.device)
+    axes = bounds_axes(lo, hi, density.shape[2:])
+    dense_xyz = torch.stack(torch.meshgrid(*axes, indexing="ij"), -1)
+    norm = ((dense_xyz.reshape(1, 1, 1, -1, 3) - lo) / (hi - lo)).flip((-1,)) * 2 - 1
+    d = F.grid_sample(density, norm, mode="bilinear", align_corners=True).reshape(dense_xyz.shape[:-1])
+    active = dense_xyz[(1 - torch.exp(-F.softplus(d + act_shift))) > bbox_thres]
+    if not len(active):
+        raise ValueError(f"alphamask_bounds: no node of the density has alpha > {bbox_thres}")
+    return active.amin(0), active.amax(0)
+
+
+def coarse_from_alphamask(cls, cfg, alphamask_rec: Dict[str, Any], device, bbox_thres: float, world_bound_scale: float,
+                          s_start: float):
+    """Start of the coarse stage from an alphamask checkpoint's "renderer" record (coarse.py:140-201): the coarse box is
+    the bounding box of the alphamask's occupied nodes, widened about its centre by ``world_bound_scale``; the alphamask's own
+    box and density become the coarse renderer's mask cache."""
+    near, far = alphamask_rec["near"], alphamask_rec["far"]
+    mask_xyz_min, mask_xyz_max = alphamask_rec["xyz_min"].to(device), alphamask_rec["xyz_max"].to(device)
+    mask_alpha_init = alphamask_rec["cfg"].app.model.alpha_init
+    mask_density = alphamask_rec["params"]["density"].to(device)
+    with torch.no_grad():
+        xyz_min, xyz_max = alphamask_bounds(mask_density, mask_xyz_min, mask_xyz_max, mask_alpha_init, bbox_thres)
+        if abs(world_bound_scale - 1) > 1e-9:
+            xyz_shift = (xyz_max - xyz_min) * (world_bound_scale - 1) / 2
+            xyz_min, xyz_max = xyz_min - xyz_shift, xyz_max + xyz_shift
+    return cls(cfg, near, far, xyz_min, xyz_max, mask_xyz_min, mask_xyz_max, mask_alpha_init, mask_density, s_start).to(device)

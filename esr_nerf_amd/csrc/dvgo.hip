@@ -64,8 +64,7 @@ __device__ __forceinline__ float dvgo_rng(int i, float u)
 // 1 - exp(-softplus(d + shift) * interval)
 __device__ __forceinline__ float dvgo_alpha(float d, float shift, float interval)
 {
-#pragma clang fp contract(off)
-    return 1.f - expf(-esr_softplus(d + shift) * interval);
+    return esr_dvgo_alpha(d, shift, interval);          // (esr_common.h: shared with esr_density_bounds)
 }
 
 // d alpha / d d, torch's autograd of dvgo_alpha (softplus backward: z / (z + 1), z = exp(x), unless x > 20)

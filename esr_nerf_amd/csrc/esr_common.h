@@ -258,6 +258,13 @@ __device__ __forceinline__ float esr_softplus(float x)
     // F.softplus(beta=1, threshold=20)
     return x > 20.f ? x : log1pf(expf(x));
 }
+// DVGO's activate_density (app/coarse/model/dvgo.py:137-138): 1 - exp(-softplus(d + shift) * interval), each operation rounded
+// on its own
+__device__ __forceinline__ float esr_dvgo_alpha(float d, float shift, float interval)
+{
+#pragma clang fp contract(off)
+    return 1.f - expf(-esr_softplus(d + shift) * interval);
+}
 __device__ __forceinline__ float esr_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 __device__ __forceinline__ int esr_lane() { return (int)(threadIdx.x & 63); }

@@ -91,9 +91,20 @@ class DenseGrid(nn.Module):
         size = tuple(int(v) for v in new_world_size)
         if self.channels == 0:
             self.grid = nn.Parameter(torch.zeros([1, self.channels, *size]))
+        elif self.grid.is_cuda:
+            # HIP resample of the channels-last memory straight into the new parameter's: no NCDHW copy, no second temporary
+            from .gridsetup import resample_grid
+            up = resample_grid(self.device_view(), size)
+            up = up.view(1, 1, *size) if self.channels == 1 else up[None].permute(0, 4, 1, 2, 3)
+            self.grid = nn.Parameter(up)
         else:
-            up = F.interpolate(self.grid.data.contiguous(), size=size, mode="trilinear", align_corners=True)
-            self.grid = nn.Parameter(self._storage(up))
+            self.grid = nn.Parameter(self._scale_volume_grid_torch(size))
+
+    def _scale_volume_grid_torch(self, size) -> torch.Tensor:
+        """The torch body (CPU-resident grids; tools/stage_setup_time.py times it against the kernel): NCDHW copy,
+        F.interpolate, back to the storage layout."""
+        up = F.interpolate(self.grid.data.contiguous(), size=size, mode="trilinear", align_corners=True)
+        return self._storage(up)
 
     def total_variation_add_grad(self, wx, wy, wz, dense_mode, mask=None):
         if mask is not None:
@@ -124,7 +135,11 @@ class MaskCache(nn.Module):
         self.xyz_max = xyz_max
         self.mask_cache_thres = cache_thres
         self.ks = ks
-        self.density = F.max_pool3d(density, kernel_size=ks, padding=ks // 2, stride=1).contiguous()
+        if density.is_cuda:
+            from .gridsetup import maxpool3d
+            self.density = maxpool3d(density, ks)
+        else:
+            self.density = F.max_pool3d(density, kernel_size=ks, padding=ks // 2, stride=1).contiguous()
         self.act_shift = math.log(1 / (1 - alpha_init) - 1)
 
     @torch.no_grad()

@@ -324,6 +324,19 @@ class VoxurfC(ForwardSwitch, nn.Module):
     def set_nonempty_mask(self):
         lin = [torch.linspace(float(self.xyz_min[i]), float(self.xyz_max[i]), self.sdf.grid.shape[2 + i],
                               device=self.xyz_min.device) for i in range(3)]
+        if self.sdf.grid.is_cuda:
+            # one HIP pass over the nodes: no [X,Y,Z,3] point tensor, the SDF pinned in the same pass
+            from .gridsetup import nonempty_mask
+            mc = self.mask_cache
+            mask, _ = nonempty_mask(mc.density, (mc.xyz_min, mc.xyz_max), mc.act_shift, mc.mask_cache_thres, lin,
+                                    sdf=self.sdf.grid.data)
+            self.nonempty_mask = mask[None, None]
+        else:
+            self._set_nonempty_mask_torch(lin)
+
+    @torch.no_grad()
+    def _set_nonempty_mask_torch(self, lin):
+        """The torch body (CPU-resident models; tools/stage_setup_time.py times it against the kernel)."""
         pts = torch.stack(torch.meshgrid(*lin, indexing="ij"), -1)
         self.nonempty_mask = self.mask_cache(pts)[None, None].contiguous()
         self.sdf.grid[~self.nonempty_mask] = 1

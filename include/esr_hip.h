@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 33
+#define ESR_ABI_VERSION 34
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -1315,6 +1315,55 @@ int esr_camera_bounds(const esr_camera_t *cam, const float *poses, float near_, 
  */
 int esr_ray_filter_cameras(const esr_scene_t *scene, const float *mask_density, const esr_camera_t *cam, const float *poses,
                            int32_t mode, float far_, int32_t n_samples, uint8_t *keep, int32_t *first_hit, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * N. Stage hand-over: grid resample, mask cache, non-empty mask, density bounds
+ * ------------------------------------------------------------------------- */
+
+#define ESR_RESAMPLE_MAX_C 16           /* esr_grid_resample: the most channels per cell                                  */
+#define ESR_DENSITY_BOUNDS_BLOCKS 1024  /* esr_density_bounds: the most workgroup partials it writes (6 floats each)      */
+
+/*
+ * Trilinear resample with align_corners=True of a channels-last grid: in [gx,gy,gz,C] -> out [ox,oy,oz,C] f32, C in
+ * 1 .. ESR_RESAMPLE_MAX_C -- replaces F.interpolate(mode="trilinear", align_corners=True) of DenseGrid.scale_volume_grid
+ * (app/utils/base/module.py:37-49) and of the fine stage's start (app/fine/fine.py:163-170) without the NCDHW copies.
+ * Per axis, every operation a separately rounded binary32 one: scale = (n_in - 1) / (n_out - 1) (0 when n_out == 1),
+ * src = scale * dst, i0 = (int)src, i1 = i0 + (i0 < n_in - 1), l1 = src - i0, l0 = 1 - l1; the blend is
+ * lx0 * (ly0 * (lz0 * v000 + lz1 * v001) + ly1 * (lz0 * v010 + lz1 * v011)) + lx1 * (the same at i1 of x), not contracted.
+ * Equal sizes copy the grid bit for bit (finite values).  in and out need 4-byte alignment only and must not overlap.
+ * Plain stores, no atomics: the same bytes on every call.
+ */
+int esr_grid_resample(const float *in, int32_t gx, int32_t gy, int32_t gz, int32_t C, float *out, int32_t ox, int32_t oy,
+                      int32_t oz, void *stream);
+/*
+ * out[x,y,z] = max of in over the ks^3 window centred on (x,y,z), clipped to the volume -- replaces
+ * F.max_pool3d(kernel_size=ks, padding=ks / 2, stride=1) of MaskCache.__init__ (module.py:92-94) on a 1-channel volume
+ * [gx,gy,gz] f32.  ks odd, 1 .. 7 (else ESR_EINVAL).  Exact: bit-equal to torch for finite and infinite inputs.
+ */
+int esr_maxpool3d(const float *in, int32_t gx, int32_t gy, int32_t gz, int32_t ks, float *out, void *stream);
+/*
+ * The non-empty mask of an SDF grid [X,Y,Z] whose nodes are (xs[i], ys[j], zs[k]) (device arrays: the torch.linspace axes
+ * of the grid's box) -- replaces MaskCache.forward over the meshgrid and the masked write of set_nonempty_mask
+ * (app/fine/model/voxurff.py:571-593, app/coarse/model/voxurfc.py:491-513).  Per node: the march's own lookup of the pooled
+ * density [mx,my,mz] in the box mask_box_host (HOST memory: min xyz then max xyz; zero padding outside),
+ * a = 1 - exp(-softplus(d + act_shift)), mask_out (u8) = a >= thres; sdf (or NULL) is set to 1 where the mask is 0 and left
+ * alone elsewhere.  The number of set cells is ADDED to *count_out (i64 on the device; the caller zeroes it).
+ */
+int esr_nonempty_mask(const float *pooled, int32_t mx, int32_t my, int32_t mz, const float *mask_box_host, float act_shift,
+                      float thres, const float *xs, const float *ys, const float *zs, int32_t X, int32_t Y, int32_t Z,
+                      float *sdf, uint8_t *mask_out, int64_t *count_out, void *stream);
+/*
+ * Bounding box of the active nodes of an alphamask density [gx,gy,gz] in the box box_host (HOST memory) -- replaces
+ * compute_bbox_by_coarse_geo (app/coarse/coarse.py:152-182).  Node (i,j,k) lies at (xs[i], ys[j], zs[k]) (device arrays of
+ * gx, gy, gz floats: lo * (1 - t) + hi * t over t = linspace(0, 1, n), the reference's dense_xyz per axis); its density is
+ * looked up there as above, a = 1 - exp(-softplus(d + act_shift)), and it is active when a > thres (strict).  out6 f32 [6]:
+ * the minimum then the maximum of the active nodes' coordinates (+inf / -inf when none is active); the number of active
+ * nodes is ADDED to *count_out (i64 on the device; the caller zeroes it).  part: f32 [ESR_DENSITY_BOUNDS_BLOCKS * 6]
+ * workspace.  Minimum, maximum and the integer count do not depend on the order: the same bytes on every call.
+ */
+int esr_density_bounds(const float *density, int32_t gx, int32_t gy, int32_t gz, const float *box_host, float act_shift,
+                       float thres, const float *xs, const float *ys, const float *zs, float *part, float *out6,
+                       int64_t *count_out, void *stream);
 
 #ifdef __cplusplus
 }
