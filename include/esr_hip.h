@@ -432,6 +432,8 @@ int esr_absmax(const float *x, int64_t n, float *out, void *stream);
  * and masks [tiles,2,64] for the 128-wide nets.  color_row0 (0, 88 or 96) selects which
  * 6-row colour group of the X tile feeds the first 6 inputs.  save == 2 keeps the masks M only (for a net
  * whose weight gradient recomputes its hidden layer: esr_tone_wgrad_recompute); H may then be NULL.
+ * M[l] is [tile][word wd][lane]: bit b of word wd in lane s + 32 h is feature 32 (2 wd + (b >> 4)) + acc_row(b & 15, h)
+ * of sample s, with acc_row(r, h) = (r & 3) + 8 (r >> 2) + 4 h.
  */
 int esr_mlp_fwd(int kind, const float *packed, const float *X, int32_t t0, int32_t t1,
                 float *const *H, uint32_t *const *M, int save, int color_row0, float *zout,
