@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libesr_hip.so")
 # developer experiments only (python -m esr_nerf_amd.build --variant builds alternative libraries; tools/ab_env.sh times them
 # side by side on one box)
 LIB_PATH = os.environ.get("ESR_LIB_PATH", LIB_PATH)
-ABI_VERSION = 34
+ABI_VERSION = 35
 _lib = None
 
 
@@ -186,6 +186,7 @@ EXPORTS = [
     "esr_adam_step_live", "esr_brick_live_from_moments",
     "esr_camera_rays", "esr_camera_batch", "esr_camera_bounds", "esr_ray_filter_cameras",
     "esr_grid_resample", "esr_maxpool3d", "esr_nonempty_mask", "esr_density_bounds",
+    "esr_cc_link", "esr_cc_flatten", "esr_cc_face_labels", "esr_cc_stats",
 ]
 
 # full ctypes signatures (argument conversion checked on every call) of the entries that declare them
@@ -217,6 +218,12 @@ SIGNATURES = {
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "esr_density_bounds": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_float, C.c_float,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esr_cc_link": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "esr_cc_flatten": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esr_cc_face_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esr_cc_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p]),
 }
 
 

@@ -312,6 +312,24 @@ class ESRNeRF(VoxurfF):
         return self._eval_query("esp", **kwargs)
 
     @torch.no_grad()
+    def surface_attributes(self, points: torch.Tensor, chunk: int = 1 << 18):
+        """What the model knows at surface points: ``points`` device [P,3] in world space, inside the bounding box ->
+        dict of device float32 tensors: ``normal`` [P,3] = normalize(grad sdf) (sample_sdf_expgrad's closed form; it points
+        outward, the side the triangles of mesh.marching_cubes face), ``sdf`` [P], ``basecolor`` [P,3], ``roughness`` [P],
+        ``metallic`` [P] (brdfnet) and ``emission`` [P,3] (emitnet on ``emit_color``, which is ``emo_color`` outside
+        fine-tune mode) -- esrnerf.py:1124-1137 per point, with the features of :1341-1348.  ``chunk``: points per pass
+        (rounded down to whole 32-point tiles)."""
+        eng = self.engine
+        points = torch.as_tensor(points, dtype=torch.float32, device=self.sdf.grid.device).reshape(-1, 3).contiguous()
+        with eng.packing():
+            for name, kind, net in (("brdf", KIND_BRDF, self.brdfnet), ("emit", KIND_EMIT, self.emitnet)):
+                lins = net.layers()
+                eng.pack(name, kind, [l.weight.detach() for l in lins], [l.bias.detach() for l in lins])
+        emit_grid = getattr(self, "emit_color", self.emo_color)
+        return eng.surface_attributes(self.scene_struct(), points, self.sdf.device_view(), emit_grid.device_view(),
+                                      self.brdf.device_view(), chunk)
+
+    @torch.no_grad()
     def forward_evaluate(self, draws=None, **kwargs):
         """Image rendering (esrnerf.py:853-1297): kwargs rays_o, rays_d, viewdirs [N,3], em_modes (one scalar), pos_rt
         [3,3], render_pbr (bool), chunk_sz (samples per light-transport chunk); uses ``self.s_val``.  Returns the

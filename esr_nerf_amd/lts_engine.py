@@ -646,6 +646,50 @@ class LtsEngine(FineEngine):
         self.range_probe()
         return out
 
+    # ------------------------------------------------------------------ surface attributes at explicit points
+    @torch.no_grad()
+    def surface_attributes(self, *args):
+        return self.healed(lambda: self._surface_attributes(*args))
+
+    def _surface_attributes(self, scene, pts, sdf, emit_grid, brdf_grid, chunk: int):
+        """Normal, SDF value, BRDF heads and emission at explicit points [P,3] (world space, inside the box), forward only:
+        the per-sample lines of esrnerf.py:1124-1137 on the features of :1341-1348, chunk by chunk in whole 32-point tiles
+        (the last tile of a chunk is padded).  -> dict of [P, c] / [P] float32 tensors."""
+        L, dev = self.L, self.device
+        n = pts.shape[0]
+        chunk = max(32, int(chunk) // 32 * 32)
+        out = dict(normal=torch.empty(n, 3, device=dev), sdf=torch.empty(n, device=dev), emission=torch.empty(n, 3, device=dev))
+        brdf = torch.empty(n, 5, device=dev)
+        sp = C.byref(scene)
+        P = self.epsp
+        for c0 in range(0, n, chunk):
+            p = pts[c0:c0 + chunk].contiguous()
+            m = p.shape[0]
+            # the normal: the closed-form gradient of sample_sdf_expgrad (border-replicated corners); the features' SDF value:
+            # sample_sdf_grad's grid_sample (zero padding) -- the same numbers anywhere inside the box
+            eg = torch.empty(m, 4, device=dev)
+            sv = torch.empty(m, 4, device=dev)
+            for zero_pad, o in ((0, eg), (1, sv)):
+                self._run("expgrad_fwd(pts)", L.esr_expgrad_fwd, sp, None, None, None, None, _lib.ptr(p), None, C.c_float(0.0),
+                          _lib.ptr(sdf), m, zero_pad, _lib.ptr(o), self._s())
+            sdf_p = sv[:, 0].contiguous()
+            vd = torch.zeros(m, 3, device=dev)             # view directions are no input of these two nets
+            self._feat_args_points(P, p, vd, sdf_p, sdf, (None, emit_grid, brdf_grid))
+            self._features(P, scene)
+            T = P.tiles_all
+            self._net_fwd(P, "emit", KIND_EMIT, 88, 0, T, save=False)
+            self._net_fwd(P, "brdf", KIND_BRDF, 96, 0, T, save=False)
+            self._act_batch("act_fwd", [dict(P=P, z="emit.z", out="emit.a", rows=4, n_ch=3, act=ACT_SOFTPLUS),
+                                        dict(P=P, z="brdf.z", out="brdf.a", rows=8, n_ch=5, act=ACT_SIGMOID)])
+            e, b = self._gather_batch([(P.bufs["emit.a"], 4, 0, 0, 3, None, m), (P.bufs["brdf.a"], 8, 0, 0, 5, None, m)])
+            out["normal"][c0:c0 + m] = torch.nn.functional.normalize(eg[:, 1:], dim=-1)
+            out["sdf"][c0:c0 + m] = sdf_p
+            out["emission"][c0:c0 + m] = e
+            brdf[c0:c0 + m] = b
+        self.range_probe()
+        out["basecolor"], out["roughness"], out["metallic"] = brdf[:, :3].contiguous(), brdf[:, 3].contiguous(), brdf[:, 4].contiguous()
+        return out
+
     # ------------------------------------------------------------------ re-lighting fine-tune (A16)
     def _with_draw_closed(self, fn, *args, **kw):
         """Run a forward that may start a surface-point draw (self._pd); whatever happens, the draw's worker is waited for

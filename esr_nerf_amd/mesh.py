@@ -4,6 +4,8 @@ libesr_hip.so's esr_mesh_* kernels (esr_nerf_amd/csrc/mesh.hip).
 ``sdf_field``       the -sdf lattice field (optional Gaussian smoothing with esr_gauss3d_fwd, then esr_mesh_field)
 ``marching_cubes``  count -> scan -> emit; vertices in index space, triangles as vertex ids, both on the device
 ``extract_geometry`` world-space numpy arrays, what the reference returns
+``connected_components`` / ``component_stats`` / ``keep_components`` / ``keep_largest``  mesh connectivity over the
+                    esr_cc_* kernels (esr_nerf_amd/csrc/meshcc.hip): device tensors in, device tensors out
 
 The lattice axes are ``torch.linspace`` as the reference builds them (plumbing: the coordinates are the torch path's bit
 for bit); the block-total scan is one ``torch.cumsum`` over 2 ceil(R^3 / 256) int64 totals.  No host copy of the field.
@@ -123,3 +125,126 @@ def extract_geometry(model, resolution=512, threshold=0.0, smooth: bool = True, 
     res = np.array(u.shape, np.float64)
     v = verts.cpu().numpy()
     return v / (res - 1.0)[None, :] * (hi - lo)[None, :] + lo[None, :], tris.cpu().numpy()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# connectivity (csrc/meshcc.hip): two selected faces are connected iff they share a vertex id
+
+
+def _check_mesh(what, triangles, n_vertices):
+    if not isinstance(triangles, torch.Tensor) or not triangles.is_cuda or triangles.dtype != torch.int64 or \
+            triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise ValueError(f"{what}: triangles must be an int64 [F, 3] device tensor")
+    n_vertices = int(n_vertices)
+    if n_vertices < 0 or n_vertices >= 2 ** 31:
+        raise ValueError(f"{what}: {n_vertices} vertices exceed the kernels' 31-bit vertex ids")
+    if triangles.numel() and (int(triangles.min()) < 0 or int(triangles.max()) >= n_vertices):
+        raise ValueError(f"{what}: a triangle names a vertex that does not exist")
+    return triangles.contiguous(), n_vertices
+
+
+@torch.no_grad()
+def connected_components(triangles: torch.Tensor, n_vertices: int, face_mask=None):
+    """Connected components of the selected faces.  triangles: device int64 [F, 3]; face_mask: device bool / uint8 [F]
+    or None (every face).  -> (face_label int32 [F] on the device, K).  Two selected faces are connected iff they share
+    a vertex id; an unselected face links nothing and gets -1.  Components are numbered 0 .. K-1 by the smallest vertex
+    id they contain, so the labels are a function of the input alone."""
+    L = _lib.lib()
+    tris, n_v = _check_mesh("connected_components", triangles, n_vertices)
+    dev, n_f = tris.device, int(tris.shape[0])
+    mask = None
+    if face_mask is not None:
+        if not isinstance(face_mask, torch.Tensor) or face_mask.device != dev or face_mask.numel() != n_f or \
+                face_mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("connected_components: face_mask must be a bool / uint8 [F] tensor on the triangles' device")
+        mask = face_mask.reshape(-1).to(torch.uint8).contiguous()
+    label = torch.empty(n_f, dtype=torch.int32, device=dev)
+    if n_f == 0 or n_v == 0:
+        return label, 0
+    with torch.cuda.device(dev):
+        s = _lib.stream_ptr(dev)
+        parent = torch.empty(n_v, dtype=torch.int32, device=dev)
+        owner = torch.empty(n_v, dtype=torch.int32, device=dev)
+        _lib.check(L.esr_cc_link(_lib.ptr(tris), _lib.ptr(mask), n_f, n_v, _lib.ptr(parent), s), "esr_cc_link")
+        _lib.check(L.esr_cc_flatten(_lib.ptr(tris), _lib.ptr(mask), n_f, n_v, _lib.ptr(parent), _lib.ptr(owner), s),
+                   "esr_cc_flatten")
+        incl = torch.cumsum(owner, 0)
+        k = int(incl[-1])
+        rank = (incl - 1).to(torch.int32)
+        _lib.check(L.esr_cc_face_labels(_lib.ptr(tris), _lib.ptr(mask), n_f, _lib.ptr(parent), _lib.ptr(rank),
+                                        _lib.ptr(label), s), "esr_cc_face_labels")
+    return label, k
+
+
+@torch.no_grad()
+def component_stats(vertices: torch.Tensor, triangles: torch.Tensor, face_label: torch.Tensor, K: int, attr=None, *,
+                    per_lane_atomics: bool = False):
+    """Per-component sums over the faces with label >= 0.  vertices: device float64 [V, 3]; face_label: device int32 [F]
+    in [-1, K); attr: device float32 [V, C], C <= 4, or None.  -> dict of device tensors: n_faces int64 [K], area,
+    area_centroid [K, 3], centroid [K, 3] = area_centroid / area, bbox_min, bbox_max [K, 3] (float64) and, with attr,
+    area_attr, mean_attr = area_attr / area [K, C] (float64) and peak float32 [K].  Counts, box and peak are exact.
+    ``per_lane_atomics``: the kernel form without the in-wave reduction (for timing; the same results)."""
+    L = _lib.lib()
+    if not isinstance(vertices, torch.Tensor) or not vertices.is_cuda or vertices.dtype != torch.float64 or \
+            vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("component_stats: vertices must be a float64 [V, 3] device tensor")
+    tris, n_v = _check_mesh("component_stats", triangles, vertices.shape[0])
+    dev, n_f, K = tris.device, int(tris.shape[0]), int(K)
+    if not isinstance(face_label, torch.Tensor) or face_label.device != dev or face_label.dtype != torch.int32 or \
+            face_label.shape != (n_f,):
+        raise ValueError("component_stats: face_label must be an int32 [F] tensor on the triangles' device")
+    if K < 0 or (n_f and (int(face_label.min()) < -1 or int(face_label.max()) >= K)):
+        raise ValueError("component_stats: a face label lies outside [-1, K)")
+    n_attr = 0
+    if attr is not None:
+        if not isinstance(attr, torch.Tensor) or attr.device != dev or attr.dtype != torch.float32 or attr.dim() != 2 or \
+                attr.shape[0] != n_v or not 1 <= attr.shape[1] <= 4:
+            raise ValueError("component_stats: attr must be a float32 [V, C] tensor, C in 1 .. 4, on the mesh's device")
+        attr, n_attr = attr.contiguous(), int(attr.shape[1])
+    f64 = dict(dtype=torch.float64, device=dev)
+    out = {"n_faces": torch.empty(K, dtype=torch.int64, device=dev), "area": torch.empty(K, **f64),
+           "area_centroid": torch.empty(K, 3, **f64), "bbox_min": torch.empty(K, 3, **f64),
+           "bbox_max": torch.empty(K, 3, **f64)}
+    if n_attr:
+        out["area_attr"] = torch.empty(K, n_attr, **f64)
+        out["peak"] = torch.empty(K, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.esr_cc_stats(_lib.ptr(vertices.contiguous()), _lib.ptr(tris), _lib.ptr(face_label.contiguous()), n_f,
+                                  K, _lib.ptr(attr), n_attr, int(bool(per_lane_atomics)), _lib.ptr(out["n_faces"]),
+                                  _lib.ptr(out["area"]), _lib.ptr(out["area_centroid"]), _lib.ptr(out["bbox_min"]),
+                                  _lib.ptr(out["bbox_max"]), _lib.ptr(out.get("area_attr")), _lib.ptr(out.get("peak")),
+                                  _lib.stream_ptr(dev)), "esr_cc_stats")
+    out["centroid"] = out["area_centroid"] / out["area"][:, None]
+    if n_attr:
+        out["mean_attr"] = out["area_attr"] / out["area"][:, None]
+    return out
+
+
+@torch.no_grad()
+def keep_components(vertices: torch.Tensor, triangles: torch.Tensor, face_keep: torch.Tensor):
+    """The mesh of the faces with ``face_keep`` (bool [F]) in their order, unreferenced vertices removed and the rest in
+    their order.  Works on any device (torch indexing and chamfer.remove_unreferenced)."""
+    from .chamfer import remove_unreferenced
+    keep = torch.as_tensor(face_keep, device=triangles.device).reshape(-1).to(torch.bool)
+    if keep.numel() != triangles.shape[0]:
+        raise ValueError("keep_components: face_keep must have one entry per face")
+    return remove_unreferenced(vertices, triangles[keep])
+
+
+@torch.no_grad()
+def keep_largest(vertices: torch.Tensor, triangles: torch.Tensor, k: int = 1, by: str = "area"):
+    """The floater filter: the mesh of the ``k`` largest connected components, by surface ``"area"`` or by ``"faces"``
+    (ties: the component with the smaller number first).  Faces and vertices keep their order."""
+    if by not in ("area", "faces"):
+        raise ValueError(f"keep_largest: by must be 'area' or 'faces', got {by!r}")
+    if k < 1:
+        raise ValueError("keep_largest: k must be >= 1")
+    label, K = connected_components(triangles, vertices.shape[0])
+    if K <= k:
+        return keep_components(vertices, triangles, label >= 0)
+    st = component_stats(vertices, triangles, label, K)
+    size = st["area"] if by == "area" else st["n_faces"]
+    order = torch.sort(size, descending=True, stable=True).indices
+    chosen = torch.zeros(K, dtype=torch.bool, device=label.device)
+    chosen[order[:k]] = True
+    return keep_components(vertices, triangles, chosen[label.long()])

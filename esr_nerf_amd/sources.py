@@ -1,0 +1,136 @@
+"""The product of a run as geometry: the extracted surface with normals, materials and emission per vertex, and the list
+of its emissive sources as connected surface patches.
+
+The reference hands its user a bare ``trimesh.Trimesh(vertices, triangles)`` (app/fine/pdra.py:781, lts.py:659,
+fine.py:632) and knows emissive sources only per view, as the image masks ``any(lin/emit > k_val)`` (pdra.py:686-688,
+911).  Here the same criterion is applied on the surface:
+
+``extract_surface``    mesh.sdf_field + mesh.marching_cubes (the smoothed field, as ``extract_geometry``), vertices moved to
+                       world space on the device, ``ESRNeRF.surface_attributes`` at the vertices (the raw grids)
+``emissive_sources``   a vertex is emissive iff max_c emission > k_val; a face is selected iff its three vertices are;
+                       the sources are the connected components of the selected faces (mesh.connected_components: two
+                       faces are connected iff they share a vertex) with mesh.component_stats of each
+``write_surface_ply``  a binary PLY with the attributes per vertex and the source id per face (chamfer.read_ply reads the
+                       mesh back)
+
+Everything up to the file is device tensors; nothing here copies the mesh to the host.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from . import mesh
+
+ATTR_KEYS = ("normal", "sdf", "basecolor", "roughness", "metallic", "emission")
+
+
+@dataclass
+class Surface:
+    vertices: torch.Tensor               # device float64 [V, 3], world space
+    triangles: torch.Tensor              # device int64 [F, 3]; (b - a) x (c - a) points outward
+    attrs: Dict[str, torch.Tensor]       # device float32: normal [V,3], sdf [V], basecolor [V,3], roughness [V], metallic [V],
+                                         # emission [V,3]
+
+
+@dataclass
+class SourceReport:
+    k_val: float
+    face_source: torch.Tensor            # device int32 [F]: the source of each face, -1 for a face in none
+    n_faces: torch.Tensor                # int64 [S]
+    area: torch.Tensor                   # float64 [S]
+    centroid: torch.Tensor               # float64 [S, 3]: area-weighted
+    bbox_min: torch.Tensor               # float64 [S, 3]
+    bbox_max: torch.Tensor               # float64 [S, 3]
+    mean_emission: torch.Tensor          # float64 [S, 3]: area-weighted
+    peak_emission: torch.Tensor          # float32 [S]: the largest emission channel at a vertex of the source
+    area_centroid: torch.Tensor          # float64 [S, 3]: the raw sum of area * face centre (centroid * area)
+    area_emission: torch.Tensor          # float64 [S, 3]: the raw sum of area * face-mean emission (mean_emission * area)
+
+    def __len__(self):
+        return int(self.n_faces.shape[0])
+
+
+@torch.no_grad()
+def extract_surface(model, resolution=512, threshold=0.0, smooth: bool = True, sigma: float = 0.5, chunk: int = 1 << 18) -> Surface:
+    """The zero level set of the model's SDF with what the model knows at every vertex.  The geometry comes from the
+    smoothed field, exactly as ``mesh.extract_geometry`` builds it (v / (R - 1) * (max - min) + min, in float64); the
+    attributes come from the raw grids (``ESRNeRF.surface_attributes``)."""
+    u = mesh.sdf_field(model, resolution, smooth, sigma)
+    verts, tris = mesh.marching_cubes(u, threshold)
+    dev = verts.device
+    lo, hi = (b.to(dev) for b in mesh._box(model))
+    res = torch.tensor(u.shape, dtype=torch.float64, device=dev)
+    # (the extent is a float32 difference, as in extract_geometry: the same bits as its numpy expression)
+    world = verts / (res - 1.0)[None, :] * (hi - lo).double()[None, :] + lo.double()[None, :]
+    # a vertex on the face of the box may round past it in float32: the attributes are those of the box's face
+    pts = torch.minimum(torch.maximum(world.float(), lo), hi)
+    attrs = model.surface_attributes(pts, chunk=chunk)
+    return Surface(world.contiguous(), tris, {k: attrs[k] for k in ATTR_KEYS})
+
+
+@torch.no_grad()
+def emissive_sources(surface: Surface, k_val: float, min_area: float = 0.0) -> SourceReport:
+    """The emissive sources of a surface as connected patches: PDRA's criterion ``any(emission > k_val)`` per vertex, the
+    faces whose three vertices pass it, their connected components (shared vertex) and the sums over each.  Sources with
+    an area under ``min_area`` are dropped: their faces get -1 and the others keep their order."""
+    v, t = surface.vertices, surface.triangles
+    em = surface.attrs["emission"].contiguous()
+    hot = em.max(dim=1).values > float(k_val)
+    sel = hot[t].all(dim=1) if t.shape[0] else torch.zeros(0, dtype=torch.bool, device=t.device)
+    label, k = mesh.connected_components(t, v.shape[0], sel)
+    st = mesh.component_stats(v, t, label, k, em)
+    if min_area > 0.0 and k:
+        keep = st["area"] >= float(min_area)
+        renum = (torch.cumsum(keep.to(torch.int32), 0) - 1).to(torch.int32)
+        renum[~keep] = -1
+        label = torch.where(label >= 0, renum[label.clamp_min(0).long()], label)
+        st = {name: x[keep] for name, x in st.items()}
+    return SourceReport(float(k_val), label, st["n_faces"], st["area"], st["centroid"], st["bbox_min"], st["bbox_max"],
+                        st["mean_attr"], st["peak"], st["area_centroid"], st["area_attr"])
+
+
+VERTEX_PROPERTIES = ["x", "y", "z", "nx", "ny", "nz", "basecolor_r", "basecolor_g", "basecolor_b", "roughness", "metallic",
+                     "emission_r", "emission_g", "emission_b"]
+
+
+def write_surface_ply(path, surface: Surface, face_source: Optional[torch.Tensor] = None):
+    """A binary little-endian PLY of the surface: per vertex ``double x y z`` then ``float nx ny nz basecolor_r/g/b
+    roughness metallic emission_r/g/b``; per face ``list uchar int vertex_indices`` and, with ``face_source``, ``int
+    source``.  ``chamfer.read_ply`` reads vertices and faces back unchanged (it skips the other properties)."""
+    a = {k: np.asarray(x.detach().cpu()) for k, x in surface.attrs.items()}
+    v = np.asarray(surface.vertices.detach().cpu(), dtype=np.float64).reshape(-1, 3)
+    t = np.asarray(surface.triangles.detach().cpu(), dtype=np.int64).reshape(-1, 3)
+    vrec = np.empty(len(v), dtype=[(p, "<f8" if p in VERTEX_PROPERTIES[:3] else "<f4") for p in VERTEX_PROPERTIES])
+    cols = np.concatenate([a["normal"].reshape(-1, 3), a["basecolor"].reshape(-1, 3), a["roughness"].reshape(-1, 1),
+                           a["metallic"].reshape(-1, 1), a["emission"].reshape(-1, 3)], axis=1)
+    for i, p in enumerate("xyz"):
+        vrec[p] = v[:, i]
+    for i, p in enumerate(VERTEX_PROPERTIES[3:]):
+        vrec[p] = cols[:, i]
+    head = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
+    head += [f"property {'double' if p in VERTEX_PROPERTIES[:3] else 'float'} {p}" for p in VERTEX_PROPERTIES]
+    head += [f"element face {len(t)}", "property list uchar int vertex_indices"]
+    fdt = [("n", "u1"), ("v", "<i4", (3,))]
+    if face_source is not None:
+        head.append("property int source")
+        fdt.append(("source", "<i4"))
+    head.append("end_header")
+    frec = np.empty(len(t), dtype=fdt)
+    frec["n"] = 3
+    frec["v"] = t
+    if face_source is not None:
+        src = np.asarray(face_source.detach().cpu() if isinstance(face_source, torch.Tensor) else face_source)
+        if src.shape != (len(t),):
+            raise ValueError("write_surface_ply: face_source must have one entry per face")
+        frec["source"] = src
+    with open(path, "wb") as f:
+        f.write(("\n".join(head) + "\n").encode("ascii"))
+        f.write(vrec.tobytes())
+        f.write(frec.tobytes())
+
+
+__all__ = ["Surface", "SourceReport", "extract_surface", "emissive_sources", "write_surface_ply", "VERTEX_PROPERTIES"]

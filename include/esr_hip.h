@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 34
+#define ESR_ABI_VERSION 35
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -1366,6 +1366,50 @@ int esr_nonempty_mask(const float *pooled, int32_t mx, int32_t my, int32_t mz, c
 int esr_density_bounds(const float *density, int32_t gx, int32_t gy, int32_t gz, const float *box_host, float act_shift,
                        float thres, const float *xs, const float *ys, const float *zs, float *part, float *out6,
                        int64_t *count_out, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * O. Surface components (connected components of a mesh, per-component sums)
+ * ------------------------------------------------------------------------- */
+
+/*
+ * Connected components of the selected faces of a triangle mesh -- what a user of the reference does on the host with
+ * trimesh.split / scipy.sparse.csgraph after trimesh.Trimesh(vertices, triangles) (app/fine/pdra.py:781, lts.py:659,
+ * fine.py:632).  triangles [n_faces,3] i64 with every id in [0, n_vertices) (the host wrapper checks: no kernel sees an id
+ * out of range); face_mask [n_faces] u8 or NULL (every face selected).
+ * Connectivity is VERTEX connectivity: two selected faces are connected iff they share a vertex id (not: an edge).  An
+ * unselected face links nothing.  A component is named by the smallest vertex id it contains; the components that own at
+ * least one selected face are numbered 0 .. K-1 in increasing order of that id, so every output below is an exact,
+ * order-independent function of the input.
+ *
+ * esr_cc_link: parent [n_vertices] i32 = v, then for every selected face union(v0, v1) and union(v0, v2), lock-free (the
+ * larger root is hooked under the smaller one by an agent-scope compare-and-swap; parents only decrease).
+ * esr_cc_flatten (its own launches: the boundary publishes parent): parent[v] = the root of v = the smallest id of v's
+ * component; owner [n_vertices] i32 = 1 for a root that owns a selected face, else 0.  rank = cumsum(owner) - 1 is the
+ * caller's (one device-wide scan), K = the last cumsum.
+ * esr_cc_face_labels: face_label [n_faces] i32 = rank[parent[triangles[f,0]]], -1 for an unselected face.
+ * ESR_ECAP for n_vertices >= 2^31; ESR_EINVAL for a pointer that is not aligned to its element.  n_faces == 0 is valid.
+ */
+int esr_cc_link(const int64_t *triangles, const uint8_t *face_mask, int64_t n_faces, int64_t n_vertices, int32_t *parent,
+                void *stream);
+int esr_cc_flatten(const int64_t *triangles, const uint8_t *face_mask, int64_t n_faces, int64_t n_vertices,
+                   int32_t *parent, int32_t *owner, void *stream);
+int esr_cc_face_labels(const int64_t *triangles, const uint8_t *face_mask, int64_t n_faces, const int32_t *parent,
+                       const int32_t *rank, int32_t *face_label, void *stream);
+/*
+ * Sums over the faces of each component.  vertices [V,3] f64; face_label [n_faces] i32 in [-1, n_components) (-1: the face
+ * takes no part); attr [V,n_attr] f32 with n_attr in 1 .. 4, or NULL with n_attr = 0.  Outputs (all written by this call,
+ * no caller initialisation), per component: n_faces_out i64; area f64 = sum 0.5 |(b - a) x (c - a)|; area_centroid f64 [3]
+ * = sum area * ((a + b) + c) / 3; bbox_min, bbox_max f64 [3] over the face vertices (+inf / -inf for a component without
+ * faces); with attr: area_attr f64 [n_attr] = sum area * (((x_a + x_b) + x_c) / 3) per channel and peak f32 = the largest
+ * attribute value at a face vertex (NULL otherwise).  Counts, box and peak are exact; the f64 sums are atomic adds of
+ * per-wave / per-block partial sums, so their last bits depend on the order of arrival.
+ * per_lane_atomics != 0 selects the form without the in-wave reduction (one atomic per face and quantity): the same
+ * results, kept for timing the reduction against it.
+ */
+int esr_cc_stats(const double *vertices, const int64_t *triangles, const int32_t *face_label, int64_t n_faces,
+                 int64_t n_components, const float *attr, int32_t n_attr, int32_t per_lane_atomics, int64_t *n_faces_out,
+                 double *area, double *area_centroid, double *bbox_min, double *bbox_max, double *area_attr, float *peak,
+                 void *stream);
 
 #ifdef __cplusplus
 }
