@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libesr_hip.so")
 # developer experiments only (python -m esr_nerf_amd.build --variant builds alternative libraries; tools/ab_env.sh times them
 # side by side on one box)
 LIB_PATH = os.environ.get("ESR_LIB_PATH", LIB_PATH)
-ABI_VERSION = 35
+ABI_VERSION = 36
 _lib = None
 
 
@@ -165,7 +165,7 @@ EXPORTS = [
     "esr_mlp_packed_floats", "esr_mlp_pack", "esr_mlp_pack_batch", "esr_mlp_packed_split_elems", "esr_mlp_split_gain_offset", "esr_mlp_split_range_flag", "esr_mlp_fwd_split", "esr_mlp_fwd_fine_split", "esr_mlp_dgrad_split", "esr_mlp_dgrad_fine_split", "esr_absmax", "esr_mlp_fwd", "esr_mlp_fwd_mixed", "esr_mlp_fwd_fine", "esr_mlp_dgrad_fine", "esr_mlp_fwd_fine_bf16", "esr_mlp_dgrad_fine_bf16", "esr_mlp_dgrad", "esr_mlp_wgrad", "esr_mlp_wgrad_batch", "esr_tone_wgrad_scratch_floats", "esr_tone_wgrad_recompute", "esr_tone_wgrad_recompute_bf16", "esr_tone_wgrad_recompute_split",
     "esr_mlp_wgrad_scratch_floats",
     "esr_fine_tone_in_fwd", "esr_fine_composite_fwd", "esr_fine_composite_bwd",
-    "esr_fine_tone_in_bwd", "esr_fine_loss_fwd_bwd_dp",
+    "esr_fine_tone_in_bwd", "esr_fine_tone_dgrad_split", "esr_fine_loss_fwd_bwd_dp",
     "esr_expgrad_fwd", "esr_expgrad_bwd", "esr_lts_dirs", "esr_lts_ref_order", "esr_lts_perturb", "esr_lts_gather_rows",
     "esr_lts_gather_points", "esr_lts_combine_fwd", "esr_lts_combine_bwd",
     "esr_act_fwd", "esr_act_bwd", "esr_act_batch", "esr_lts_gather_rows_batch", "esr_pair_loss_batch", "esr_lts_ref_order_inv", "esr_lts_dirs_rays", "esr_composite3_fwd", "esr_composite3_bwd", "esr_lts_tone_in_bwd",

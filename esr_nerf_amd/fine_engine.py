@@ -114,8 +114,8 @@ class _Workspace:
     ``FineEngine._march_plan`` asks of a workspace (lts_engine.Pass offers the same)."""
     min_tiles = 0                     # nothing is allocated for a march without survivors
 
-    def __init__(self, device, rows=FINE_ROWS, other=FINE_OTHER):
-        self.device, self.rows, self.other = device, rows, other
+    def __init__(self, device, rows=FINE_ROWS, other=FINE_OTHER, lazy=()):
+        self.device, self.rows, self.other, self.lazy = device, rows, other, frozenset(lazy)
         self.cap_tiles = 0
         self.buf: Dict[str, torch.Tensor] = {}
         self.ray_bufs: Dict[int, Dict[str, torch.Tensor]] = {}
@@ -125,12 +125,15 @@ class _Workspace:
         if tiles <= self.cap_tiles:
             return
         cap = int(max(tiles, self.cap_tiles) * 1.25) + 64          # (headroom from the first allocation on: lts_engine.Pass.ensure)
-        self.buf = {k: torch.empty(cap * r * 32, dtype=torch.float32, device=self.device) for k, r in self.rows.items()}
+        self.buf = {k: torch.empty(cap * r * 32, dtype=torch.float32, device=self.device) for k, r in self.rows.items()
+                    if k not in self.lazy}
         for k, (per_tile, dtype) in self.other.items():
             self.buf[k] = torch.empty(cap * per_tile, dtype=dtype, device=self.device)
         self.cap_tiles = cap
 
     def __getitem__(self, k):
+        if k not in self.buf and k in self.lazy:                   # a lazy buffer: allocated by its first reader
+            self.buf[k] = torch.empty(self.cap_tiles * self.rows[k] * 32, dtype=torch.float32, device=self.device)
         return self.buf[k]
 
     def rec_ray_now(self):
@@ -191,6 +194,9 @@ class _PackGroup:
 
 
 class FineEngine:
+    # split engine: the tone mapper's input gradients end with tone_in_bwd's contraction (one launch, no dXt); False: the two launches
+    fused_tone_dgrad = True
+
     def __init__(self, device, mlp_dtype: str = "f32"):
         """``mlp_dtype``: "f32" (f32 matrix cores; BASELINE configs C2, C4) or "bf16" (bf16 MFMA operands with fp32
         accumulation for the MLPs only -- the build-side precision choice of C3 / C5; everything else stays fp32)."""
@@ -201,7 +207,8 @@ class FineEngine:
         self.packed16: Dict[str, torch.Tensor] = {}
         self._p16: Dict[int, C.c_void_p] = {}
         self.L = _lib.lib()
-        self.ws = _Workspace(self.device)
+        # dXt (8 KB per tile) only exists on the two-launch tone path: the bf16 engine, the f32 MFMA fallback, ``fused_tone_dgrad`` off
+        self.ws = _Workspace(self.device, lazy=("dXt",))
         self.plan_dev = torch.zeros(8, dtype=torch.int32, device=self.device)
         self.plan_host = torch.zeros(8, dtype=torch.int32).pin_memory()
         self.packed = {
@@ -761,7 +768,7 @@ class FineEngine:
         s = self._s()
         dweight = ws["dweight"] if ta > 0 else torch.zeros(32, dtype=torch.float32, device=self.device)
         # Queues (HIP streams of this device):
-        #   main     composite_bwd -> march_bwd -> dgrad(tone) -> tone_in_bwd -> dgrad(rad) -> feat_bwd
+        #   main     composite_bwd -> march_bwd -> dgrad(tone) [-> tone_in_bwd] -> dgrad(rad) -> feat_bwd
         #   wgrad    (overlap_wgrad) the weight gradients, after dgrad(rad), beside the feature scatter
         # (a third stream for the scatters was measured slower on MI355X -- C2: 4.08 ms without, 4.19-4.47 ms with: the
         #  atomics-heavy scatters slow the matrix kernels more than they hide -- and is gone)
@@ -827,6 +834,11 @@ class FineEngine:
         if self.bf16:
             self._run("mlp_dgrad(tone)", L.esr_mlp_dgrad_bf16, KIND_TONEMAP, self._p16[self.packed["tone"].data_ptr()],
                       _lib.ptr(ws["dzt"]), 0, ta, self._H(["Mt"]), dZt_arg, _lib.ptr(ws["dXt"]), s)
+        elif split and self.fused_tone_dgrad:
+            # the tone mapper's input gradients end each tile with tone_in_bwd's contraction: dzt -> dz, no dXt in memory
+            self._run("mlp_dgrad(tone)", L.esr_fine_tone_dgrad_split, _lib.ptr(self.packed_split["tone"]), _lib.ptr(ws["dzt"]),
+                      _lib.ptr(ws["Mt"]), _lib.ptr(ws["Xt"]), _lib.ptr(g_lin), _lib.ptr(ws["z_off"]), _lib.ptr(ws["z_emo"]),
+                      _lib.ptr(ws["rec_ray"]), _lib.ptr(ws["rec_w"]), to, ta, _lib.ptr(ws["dz"]), _lib.ptr(ctx.amax_t), s)
         elif split:
             # (the split kernels leave max |dzt| / max |dz| x the nets' gain bounds behind: the weight gradients' scales)
             self._run("mlp_dgrad(tone)", L.esr_mlp_dgrad_split, KIND_TONEMAP, _lib.ptr(self.packed_split["tone"]), _lib.ptr(ws["dzt"]),
@@ -834,9 +846,10 @@ class FineEngine:
         else:
             self._run("mlp_dgrad(tone)", L.esr_mlp_dgrad, KIND_TONEMAP, _lib.ptr(self.packed["tone"]), _lib.ptr(ws["dzt"]), 0, ta,
                       self._H(["Mt"]), dZt_arg, _lib.ptr(ws["dXt"]), s)
-        self._run("tone_in_bwd", L.esr_fine_tone_in_bwd, _lib.ptr(ws["dXt"]), _lib.ptr(ws["Xt"]), _lib.ptr(g_lin), _lib.ptr(ws["lin"]),
-                  _lib.ptr(ws["z_off"]), _lib.ptr(ws["z_emo"]), _lib.ptr(ws["rec_ray"]), _lib.ptr(ws["rec_w"]), to, ta,
-                  _lib.ptr(ws["dz"]), s)
+        if self.bf16 or not (split and self.fused_tone_dgrad):
+            self._run("tone_in_bwd", L.esr_fine_tone_in_bwd, _lib.ptr(ws["dXt"]), _lib.ptr(ws["Xt"]), _lib.ptr(g_lin),
+                      _lib.ptr(ws["lin"]), _lib.ptr(ws["z_off"]), _lib.ptr(ws["z_emo"]), _lib.ptr(ws["rec_ray"]),
+                      _lib.ptr(ws["rec_w"]), to, ta, _lib.ptr(ws["dz"]), s)
         # both radiance nets' input gradients: one launch
         if self.bf16:
             pe, po = self.packed["emo"].data_ptr(), self.packed["off"].data_ptr()

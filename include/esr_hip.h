@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 35
+#define ESR_ABI_VERSION 36
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -593,6 +593,15 @@ int esr_fine_tone_in_bwd(const float *dXt, const float *Xt, const float *g_lin, 
                          const float *z_off, const float *z_emo, const int32_t *rec_ray,
                          const float *rec_w, int32_t tiles_on, int32_t tiles_all, float *dz,
                          void *stream);
+/*
+ * esr_mlp_dgrad_split(ESR_MLP_TONEMAP, ..., dZ = {NULL}) over tiles [0, tiles_all) and esr_fine_tone_in_bwd as ONE launch: the
+ * input-gradient kernel ends each tile with the contraction instead of storing dXt, which is never in memory.  planes: the tone
+ * mapper's split planes; dzt [tiles,4,32], Mt: its output gradients and ReLU mask words; the remaining arguments and dz as
+ * esr_fine_tone_in_bwd; amax as esr_mlp_dgrad_split (max |dzt| x the gain factor, for the tone mapper's weight gradients).
+ */
+int esr_fine_tone_dgrad_split(const void *planes, const float *dzt, const uint32_t *Mt, const float *Xt, const float *g_lin,
+                              const float *z_off, const float *z_emo, const int32_t *rec_ray, const float *rec_w,
+                              int32_t tiles_on, int32_t tiles_all, float *dz, float *amax, void *stream);
 
 /*
  * Trainer-step loss of the fine stage (app/fine/fine.py:355-382) and its
