@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libesr_hip.so")
 # developer experiments only (python -m esr_nerf_amd.build --variant builds alternative libraries; tools/ab_env.sh times them
 # side by side on one box)
 LIB_PATH = os.environ.get("ESR_LIB_PATH", LIB_PATH)
-ABI_VERSION = 36
+ABI_VERSION = 37
 _lib = None
 
 
@@ -138,6 +138,13 @@ CAMERA_LDS_VIEWS = 256                  # ESR_CAMERA_LDS_VIEWS
 CAMERA_BOUNDS_BLOCKS = 1024             # ESR_CAMERA_BOUNDS_BLOCKS
 RESAMPLE_MAX_C = 16                     # ESR_RESAMPLE_MAX_C
 DENSITY_BOUNDS_BLOCKS = 1024            # ESR_DENSITY_BOUNDS_BLOCKS
+PARTITION_BLOCK = 1024                  # ESR_PARTITION_BLOCK
+PARTITION_SCAN_TILE = 1024              # ESR_PARTITION_SCAN_TILE
+
+
+class EsrRegroupStats(C.Structure):     # esr_regroup_stats_t
+    _fields_ = [(n, C.c_int64) for n in ("n_set", "n_clear", "n_nan")] + \
+               [(n, C.c_float) for n in ("min_all", "max_all", "min_set", "max_set", "min_clear", "max_clear")]
 
 
 class EsrMlpWeights(C.Structure):
@@ -187,6 +194,7 @@ EXPORTS = [
     "esr_camera_rays", "esr_camera_batch", "esr_camera_bounds", "esr_ray_filter_cameras",
     "esr_grid_resample", "esr_maxpool3d", "esr_nonempty_mask", "esr_density_bounds",
     "esr_cc_link", "esr_cc_flatten", "esr_cc_face_labels", "esr_cc_stats",
+    "esr_emit_decide", "esr_flag_scan", "esr_index_partition",
 ]
 
 # full ctypes signatures (argument conversion checked on every call) of the entries that declare them
@@ -224,6 +232,9 @@ SIGNATURES = {
     "esr_cc_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p]),
+    "esr_emit_decide": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "esr_flag_scan": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esr_index_partition": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

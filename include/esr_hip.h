@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 36
+#define ESR_ABI_VERSION 37
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -1419,6 +1419,50 @@ int esr_cc_stats(const double *vertices, const int64_t *triangles, const int32_t
                  int64_t n_components, const float *attr, int32_t n_attr, int32_t per_lane_atomics, int64_t *n_faces_out,
                  double *area, double *area_centroid, double *bbox_min, double *bbox_max, double *area_attr, float *peak,
                  void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * P. PDRA ray re-split (update_ray_groups): decide, count, partition
+ * ------------------------------------------------------------------------- */
+
+#define ESR_PARTITION_BLOCK 1024      /* flags (rows) per tile of esr_flag_scan / esr_index_partition                       */
+#define ESR_PARTITION_SCAN_TILE 1024  /* tile counts per trip of the one-block scan launch of esr_flag_scan                 */
+
+/* What app/fine/pdra.py:912-925 prints, plus the counts.  Minima and maxima run over the non-NaN elements ([n,3] values,
+ * not per-ray maxima) of all rays, of the set (uncertain) rays and of the clear (certain) rays; an empty group holds +inf
+ * and -inf.  -0.0 orders below +0.0.  n_nan = rays with a NaN channel (they are clear, so n_set + n_clear = n). */
+typedef struct esr_regroup_stats_t {
+    int64_t n_set, n_clear, n_nan;
+    float min_all, max_all, min_set, max_set, min_clear, max_clear;
+} esr_regroup_stats_t;
+
+/*
+ * flags[i] = max_c emission[i][c] > k_val, compared as binary32 -- app/fine/pdra.py:911
+ * (uncert_masks = torch.max(emission, dim=-1)[0] > k_val) with the statistics of :912-925 in the same pass.  emission
+ * [n,3] f32, flags u8 [n] (any alignment), stats: DEVICE memory.  A ray with a NaN channel is not set (torch.max propagates
+ * the NaN and NaN > k is false).  accumulate == 0: *stats is overwritten; accumulate != 0: the call merges into what
+ * *stats holds (chunk by chunk over one flag vector, no [n,3] buffer).  Counts, minima and maxima are exact and do not
+ * depend on the order of arrival.
+ * All three entries of this section: n == 0 is success and touches no pointer; n >= 2^31 is ESR_ECAP; a NULL or
+ * misaligned pointer is ESR_EINVAL; everything is enqueued on `stream` and nothing waits on the host.
+ */
+int esr_emit_decide(const float *emission, int64_t n, float k_val, uint8_t *flags, esr_regroup_stats_t *stats,
+                    int accumulate, void *stream);
+/*
+ * Counts for the partition below (two launches: a count per tile, then a one-block exclusive scan).  block_offsets i64
+ * [ceil(n / ESR_PARTITION_BLOCK)]: the number of set (non-zero) flags in front of tile b; totals i64 [2] = (set, clear).
+ * Replaces the counting inside the boolean indexings of utils2/utils.py:257-267.
+ */
+int esr_flag_scan(const uint8_t *flags, int64_t n, int64_t *block_offsets, int64_t *totals, void *stream);
+/*
+ * The stable two-way partition of RayGroupManager.filter (utils2/utils.py:264-267): set_out [totals[0]] = rows[flags != 0]
+ * and clear_out [totals[1]] = rows[flags == 0], both in input order.  rows i64 [n] is not written; set_out and clear_out
+ * must not alias it or each other; clear_out may point into the middle of a larger buffer (the certain group's new vector,
+ * behind its old contents).  flags and block_offsets as esr_flag_scan left them.  An output of size 0 may be NULL: the
+ * CALLER guarantees that a NULL output's side is empty (totals says so); the kernel cannot check it and skips the stores of
+ * rows that would go to a NULL output, only two NULL outputs are ESR_EINVAL.
+ */
+int esr_index_partition(const int64_t *rows, const uint8_t *flags, const int64_t *block_offsets, int64_t n,
+                        int64_t *set_out, int64_t *clear_out, void *stream);
 
 #ifdef __cplusplus
 }
