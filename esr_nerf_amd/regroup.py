@@ -1,11 +1,13 @@
 """PDRA's ray re-split: which uncertain rays stay uncertain -- ``update_ray_groups`` of the reference's PDRA trainer
 (app/fine/pdra.py:882-932) with ``RayGroupManager.filter`` (utils2/utils.py:234-267) -- over the kernels of
-esr_nerf_amd/csrc/regroup.hip.
+esr_nerf_amd/csrc/regroup.hip and, for the re-split under data parallelism, csrc/regroup_dp.hip.
 
 ``decide``             emission [n, 3] -> one flag per ray (``max_c emission > k_val``) and the statistics the reference
                        prints, in one launch; chunk after chunk into one flag vector and one statistics record
 ``partition``          rows, flags -> ``(rows[flags], rows[~flags])``, both in input order (count, scan, scatter)
-``apply_flags``        what ``sampler.filter(flags)`` does, for a ``RayGroupManager`` or a ``CameraRayGroupManager``
+``apply_flags``        what ``sampler.filter(flags)`` does, for a ``RayGroupManager`` or a ``CameraRayGroupManager``; byte flags
+                       or (``packed=True``) 64-bit words
+``ray_share``          the rays of the uncertain group a rank decides; ``pack_flags`` / ``unpack_flags``: bytes <-> words
 ``update_ray_groups``  the trainer's method: ``eval_emit`` over the uncertain group in chunks, ``decide`` per chunk,
                        ``apply_flags`` once, the reference's printed lines -> ``RegroupReport``
 
@@ -22,14 +24,23 @@ Fine-tune mode.  The mode is put back as ``relight.EditRaySelector`` does, with 
 the middle of a fine-tune replaces the frozen emission grid by the trained one.  The PDRA trainer re-splits in plain
 training mode only (pdra.py:219, :372).
 
-Data parallelism is not implemented here, but the seam is fixed: the groups change ONLY through ``apply_flags``, which is a
-deterministic function of the flags.  With ``world > 1`` every rank holds the full index vectors, so all ranks MUST call
-``apply_flags`` with the SAME flags -- one rank's flags broadcast, or per-rank shares all-gathered -- never with flags each
-rank decided for itself (a ray on the boundary may be decided differently by two ranks, and the index vectors would diverge).
-``update_ray_groups`` on a sampler with ``world > 1`` therefore raises ``NotImplementedError``.
+Data parallelism.  The groups change ONLY through ``apply_flags``, which is a deterministic function of the flags.  With
+``world > 1`` every rank holds the full index vectors, so all ranks MUST call ``apply_flags`` with the SAME flags -- never with
+flags each rank decided for itself on the same ray (a ray on the boundary may be decided differently by two ranks, and the
+index vectors would diverge).  ``update_ray_groups(..., process_group=pg)`` does it so: rank r evaluates ``eval_emit`` on its
+share ``ray_share(n, r, world)`` of the uncertain group only -- shares are disjoint and start on multiples of 64 rays -- and
+decides it into its 64-bit words (one bit per ray, ``esr_emit_decide_bits``: a wave's ballot) of ONE int64 device buffer
+``[W flag words | world statistics records | merged record | totals | failures]`` that is zero outside what the rank owns.
+ONE ``all_reduce(SUM)`` of that buffer is then the union of the decisions and the gather of the records (zero plus bits is
+bits, for the float fields too) and carries the failure count; ``esr_regroup_stats_merge``, ``esr_flag_scan_bits`` and
+``esr_index_partition_bits`` follow on the words, and the ONE read-back (72 bytes: record, totals, failures) precedes the
+allocation.  No ray is decided by two ranks, so nothing depends on two ranks agreeing to the last bit.  A rank whose
+``eval_emit`` raises still joins the collective with its failure word set, and EVERY rank raises, its groups untouched.
+``update_ray_groups`` on a sampler with ``world > 1`` and no process group raises ``NotImplementedError``.
 
 There is no CPU kernel: ``decide`` and ``partition`` raise on CPU tensors.  ``update_ray_groups`` with a renderer on the CPU
-(a stub in the tests) takes the reference's torch statements for the decision.
+(a stub in the tests) takes the reference's torch statements for the decision, under a process group with the same shares:
+one SUM all-reduce of a zero-filled uint8 vector (the flags, one byte each, then every rank's record and failure byte).
 """
 from __future__ import annotations
 
@@ -166,36 +177,198 @@ def partition(rows: torch.Tensor, flags: torch.Tensor) -> Tuple[torch.Tensor, to
     return set_rows, clear_rows
 
 
+def n_words(n: int) -> int:
+    """64-bit words of ``n`` packed flags"""
+    return (int(n) + 63) // 64
+
+
+def ray_share(n: int, rank: int, world: int) -> Tuple[int, int]:
+    """The rays ``[lo, hi)`` of ``n`` that ``rank`` of ``world`` decides: with ``W = ceil(n / 64)`` words the rank owns the
+    words ``[W * rank // world, W * (rank + 1) // world)``.  The shares are disjoint, in rank order and cover ``[0, n)``;
+    every share starts on a word (a multiple of 64 rays); sizes differ by at most 64; a share is empty when ``W < world``
+    leaves the rank no word."""
+    if not 0 <= rank < world:
+        raise ValueError(f"ray_share: rank {rank} of {world}")
+    w = n_words(n)
+    return 64 * (w * rank // world), min(int(n), 64 * (w * (rank + 1) // world))
+
+
+def _check_words(what: str, words: torch.Tensor, n: int):
+    if words.dtype != torch.int64 or words.dim() != 1 or not words.is_contiguous() or len(words) != n_words(n):
+        raise ValueError(f"{what}: {n} packed flags are a contiguous int64 vector of {n_words(n)} words, got {words.dtype} "
+                         f"{tuple(words.shape)}")
+
+
+_BIT = None
+
+
+def _bits() -> torch.Tensor:
+    global _BIT
+    if _BIT is None:
+        _BIT = torch.arange(64, dtype=torch.int64)
+    return _BIT
+
+
 @torch.no_grad()
-def apply_flags(sampler, flags: torch.Tensor, stats: Optional[torch.Tensor] = None) -> Optional[Dict[str, float]]:
-    """``sampler.filter(flags)``: a set flag keeps its ray uncertain, a clear one moves it to the END of the certain group;
-    ``uncert_batch_st`` and ``cert_batch_st`` stay as they are.  ``flags`` is aligned with the uncertain group's current
-    order.  Index vectors on the device: scan, one read-back (of ``stats`` when given, whose last two words take the
-    totals), exact-size allocation, a device copy of the old certain vector, the partition.  A ``data_preload: cpu`` sampler:
-    the existing ``filter`` lines.  With ``world > 1`` all ranks must pass the SAME flags (module docstring).
-    Returns ``read_stats(stats)`` when ``stats`` is given."""
-    rows, old = sampler.uncert_data_idxs, sampler.cert_data_idxs
-    if len(flags) != len(rows):
-        raise ValueError(f"apply_flags: {len(flags)} flags for an uncertain group of {len(rows)} rays")
-    if not rows.is_cuda:
-        host = read_stats(stats) if stats is not None else None
-        sampler.filter(flags.view(torch.bool) if flags.dtype == torch.uint8 else flags)
-        return host
-    _need_device("apply_flags", flags)
-    _check_rows("apply_flags", rows, flags)
-    dev = rows.device
+def pack_flags(flags: torch.Tensor, words: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bool / uint8 flags [n] -> int64 words [ceil(n / 64)]: bit ``b`` of word ``w`` is flag ``64 w + b`` (bit 0 the least
+    significant), a non-zero byte is a set bit, the tail of the last word is clear.  Device flags: ``esr_flags_pack`` on the
+    current stream, into ``words`` when given; CPU flags: torch statements."""
     f = _u8(flags)
+    n = int(f.numel())
+    if words is None:
+        words = torch.empty(n_words(n), dtype=torch.int64, device=f.device)
+    _check_words("pack_flags", words, n)
+    if words.device != f.device:
+        raise ValueError(f"pack_flags: flags on {f.device}, words on {words.device}")
+    if not f.is_cuda:
+        pad = torch.zeros(len(words) * 64, dtype=torch.int64)
+        pad[:n] = f != 0
+        words.copy_((pad.view(-1, 64) << _bits()).sum(1))         # (bit 63 wraps into the sign, as it must)
+        return words
+    with torch.cuda.device(f.device):
+        _lib.check(_lib.lib().esr_flags_pack(_lib.ptr(f), n, _lib.ptr(words), _lib.stream_ptr(f.device)), "esr_flags_pack")
+    return words
+
+
+@torch.no_grad()
+def unpack_flags(words: torch.Tensor, n: int, flags: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 words -> bool flags [n] (bytes of exactly 0 or 1), into ``flags`` (bool or uint8) when given; the inverse of
+    ``pack_flags``"""
+    n = int(n)
+    _check_words("unpack_flags", words, n)
+    if flags is None:
+        flags = torch.empty(n, dtype=torch.bool, device=words.device)
+    f = _u8(flags)
+    if len(f) != n or f.device != words.device:
+        raise ValueError(f"unpack_flags: {n} flags on {words.device}, got {tuple(f.shape)} on {f.device}")
+    if not words.is_cuda:
+        f.copy_(((words[:, None] >> _bits()) & 1).view(-1)[:n])
+    else:
+        with torch.cuda.device(words.device):
+            _lib.check(_lib.lib().esr_flags_unpack(_lib.ptr(words), n, _lib.ptr(f), _lib.stream_ptr(words.device)),
+                       "esr_flags_unpack")
+    return flags if flags.dtype == torch.bool else flags.view(torch.bool)
+
+
+@torch.no_grad()
+def decide_bits(emission: torch.Tensor, k_val: float, words: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None):
+    """``decide`` with the flags as packed words: emission [n, 3] -> ``(words, stats)``, ``words`` int64 [ceil(n / 64)] (a
+    given vector may be a slice of a longer one: a chunk that starts on a multiple of 64 rays starts on a word), ``stats`` as
+    ``decide`` treats it.  One launch, not waited for."""
+    _need_device("decide_bits", emission)
+    if emission.dim() != 2 or emission.shape[1] != 3 or emission.dtype != torch.float32:
+        raise ValueError(f"decide_bits: emission is [n, 3] float32, got {emission.dtype} {tuple(emission.shape)}")
+    dev = emission.device
+    e = emission.contiguous()
+    n = int(e.shape[0])
     with torch.cuda.device(dev):
-        buf = stats if stats is not None else new_stats(dev)
-        off = _scan(f, buf[_STATS_WORDS:])
-        host = read_stats(buf)
-        n_set, n_clear = host["totals"]
+        if words is None:
+            words = torch.empty(n_words(n), dtype=torch.int64, device=dev)
+        _check_words("decide_bits", words, n)
+        accumulate = stats is not None
+        if stats is None:
+            stats = new_stats(dev)
+            if n == 0:
+                stats.copy_(_identity().to(dev))
+        _lib.check(_lib.lib().esr_emit_decide_bits(_lib.ptr(e), n, float(k_val), _lib.ptr(words), _lib.ptr(stats),
+                                                   int(accumulate), _lib.stream_ptr(dev)), "esr_emit_decide_bits")
+    return words, stats
+
+
+def merge_stats(parts: torch.Tensor, n_parts: int, out: torch.Tensor):
+    """``esr_regroup_stats_merge``: the ``n_parts`` records at the front of the int64 device vector ``parts`` (6 words each)
+    into the record at the front of ``out``; one launch, not waited for"""
+    _need_device("merge_stats", parts, out)
+    if parts.dtype != torch.int64 or out.dtype != torch.int64 or len(parts) < _STATS_WORDS * n_parts or len(out) < _STATS_WORDS:
+        raise ValueError(f"merge_stats: {n_parts} records of {_STATS_WORDS} int64 words, got {tuple(parts.shape)} -> {tuple(out.shape)}")
+    with torch.cuda.device(parts.device):
+        _lib.check(_lib.lib().esr_regroup_stats_merge(_lib.ptr(parts), int(n_parts), _lib.ptr(out),
+                                                      _lib.stream_ptr(parts.device)), "esr_regroup_stats_merge")
+
+
+def _scan_bits(words: torch.Tensor, n: int, totals: torch.Tensor) -> torch.Tensor:
+    dev = words.device
+    off = torch.empty((n + _lib.PARTITION_BLOCK - 1) // _lib.PARTITION_BLOCK, dtype=torch.int64, device=dev)
+    if n == 0:
+        totals.zero_()
+    _lib.check(_lib.lib().esr_flag_scan_bits(_lib.ptr(words), n, _lib.ptr(off), _lib.ptr(totals), _lib.stream_ptr(dev)),
+               "esr_flag_scan_bits")
+    return off
+
+
+def _scatter_bits(rows, words, off, set_out, clear_out):
+    dev = rows.device
+    _lib.check(_lib.lib().esr_index_partition_bits(_lib.ptr(rows), _lib.ptr(words), _lib.ptr(off), int(rows.numel()),
+                                                   _lib.ptr(set_out), _lib.ptr(clear_out), _lib.stream_ptr(dev)),
+               "esr_index_partition_bits")
+
+
+class RemoteFailure(RuntimeError):
+    """A re-split under a process group in which a rank's ``eval_emit`` raised: every rank raises, its groups untouched"""
+
+
+def _raise_if_failed(n_failed: int):
+    if n_failed:
+        raise RemoteFailure(f"update_ray_groups: eval_emit failed on {n_failed} rank(s) of the process group; no rank's "
+                            f"groups were changed")
+
+
+def _partition_into_sampler(sampler, f: torch.Tensor, packed: bool, buf: torch.Tensor):
+    """Index vectors on the device: scan into the totals of ``buf`` (int64: record, totals, and for a re-split under a
+    process group the failure count), ONE read-back of ``buf``, exact-size allocation, the partition -> ``buf`` on the host"""
+    rows, old = sampler.uncert_data_idxs, sampler.cert_data_idxs
+    dev = rows.device
+    n = len(rows)
+    with torch.cuda.device(dev):
+        totals = buf[_STATS_WORDS:_STATS_WORDS + 2]
+        off = _scan_bits(f, n, totals) if packed else _scan(f, totals)
+        host = buf.cpu().numpy()
+        if len(host) > _STATS_WORDS + 2:
+            _raise_if_failed(int(host[_STATS_WORDS + 2]))
+        n_set, n_clear = int(host[_STATS_WORDS]), int(host[_STATS_WORDS + 1])
         new_u = torch.empty(n_set, dtype=torch.int64, device=dev)
         new_c = torch.empty(len(old) + n_clear, dtype=torch.int64, device=dev)
         new_c[:len(old)].copy_(old)
-        _scatter(rows.contiguous(), f, off, new_u, new_c[len(old):])
+        (_scatter_bits if packed else _scatter)(rows.contiguous(), f, off, new_u, new_c[len(old):])
     sampler.uncert_data_idxs, sampler.cert_data_idxs = new_u, new_c
-    return host if stats is not None else None
+    return host
+
+
+@torch.no_grad()
+def apply_flags(sampler, flags: torch.Tensor, stats: Optional[torch.Tensor] = None, *,
+                packed: bool = False) -> Optional[Dict[str, float]]:
+    """``sampler.filter(flags)``: a set flag keeps its ray uncertain, a clear one moves it to the END of the certain group;
+    ``uncert_batch_st`` and ``cert_batch_st`` stay as they are.  ``flags`` is aligned with the uncertain group's current
+    order: a bool / uint8 vector with one entry per ray, or with ``packed=True`` the int64 vector of ``ceil(n / 64)`` words of
+    ``pack_flags`` (said by the keyword, never guessed from a dtype).  Index vectors on the device: scan, one read-back (of
+    ``stats`` when given, whose last two words take the totals), exact-size allocation, a device copy of the old certain
+    vector, the partition.  A ``data_preload: cpu`` sampler: the existing ``filter`` lines (on unpacked flags).  With
+    ``world > 1`` all ranks must pass the SAME flags (module docstring).  Returns ``read_stats(stats)`` when ``stats`` is given."""
+    rows = sampler.uncert_data_idxs
+    if packed:
+        _check_words("apply_flags", flags, len(rows))
+    elif len(flags) != len(rows):
+        raise ValueError(f"apply_flags: {len(flags)} flags for an uncertain group of {len(rows)} rays")
+    elif flags.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"apply_flags: flags are bool / uint8, one per ray (packed words need packed=True), got {flags.dtype}")
+    if not rows.is_cuda:
+        host = read_stats(stats) if stats is not None else None
+        if packed:
+            flags = unpack_flags(flags, len(rows))
+        sampler.filter(flags.view(torch.bool) if flags.dtype == torch.uint8 else flags)
+        return host
+    _need_device("apply_flags", flags)
+    if packed:
+        if flags.device != rows.device or rows.dtype != torch.int64 or rows.dim() != 1:
+            raise ValueError(f"apply_flags: int64 rows and their words on one device, got {rows.dtype} on {rows.device} and "
+                             f"words on {flags.device}")
+        f = flags
+    else:
+        _check_rows("apply_flags", rows, flags)
+        f = _u8(flags)
+    host = _partition_into_sampler(sampler, f, packed, stats if stats is not None else new_stats(rows.device))
+    return _parse_stats(host) if stats is not None else None
 
 
 def _merge(a: Optional[Dict[str, float]], b: Dict[str, float]) -> Dict[str, float]:
@@ -247,22 +420,53 @@ def _stats_line(sampler) -> str:
     return f"uncertain: {nu}\t certain: {nc}\t uncertain/all: {share}"
 
 
+def _mode_of(renderer):
+    was_training = renderer.training
+    return was_training, was_training and getattr(renderer, "forward", None) == getattr(renderer, "forward_finetune", None)
+
+
+def _restore_mode(renderer, was_training: bool, finetune: bool):
+    if was_training:
+        renderer.train(True, finetune=True) if finetune else renderer.train(True)
+
+
+def _print_after(sampler, n: int, stats: Dict[str, float]):
+    # pdra.py:912-925; the reference prints the three pairs only for a non-empty selection
+    if n:
+        print("emission(max, min):", stats["max_all"], stats["min_all"])
+    if stats["n_set"]:
+        print("emission_uncert_masks(max, min):", stats["max_set"], stats["min_set"])
+    if stats["n_clear"]:
+        print("emission_cert_masks(max, min):", stats["max_clear"], stats["min_clear"])
+    print("[NEW MASK UPDATE]\n" + _stats_line(sampler))
+
+
 @torch.no_grad()
 def update_ray_groups(renderer, sampler, k_val: float, batch_size: Optional[int] = None, verbose: bool = True,
-                      return_emission: bool = False) -> RegroupReport:
+                      return_emission: bool = False, process_group=None) -> RegroupReport:
     """pdra.py:882-932: ``renderer.eval_emit`` on every ray of the sampler's uncertain group in its current order,
     ``batch_size`` rays per pass (None: ``DEFAULT_BATCH_SIZE``); a ray stays uncertain iff ``max_c emission > k_val``, all
     others go to the end of the certain group.  The renderer is in ``eval()`` for the duration and gets its mode (train or
     fine-tune) back afterwards, also when ``eval_emit`` raises.  No [n, 3] emission buffer is kept unless
-    ``return_emission``.  ``verbose`` prints the reference's lines."""
-    if getattr(sampler, "world", 1) > 1:
+    ``return_emission``.  ``verbose`` prints the reference's lines.
+
+    ``process_group`` (a ``torch.distributed`` group of ``sampler.world`` ranks, this one ``sampler.rank``): the re-split
+    under data parallelism of the module docstring.  Every rank evaluates only ``ray_share(n, rank, world)``, in chunks of
+    ``batch_size`` rounded up to a multiple of 64; one all-reduce; every rank ends with the same groups, report counts,
+    statistics and ``flags`` (the full vector).  ``return_emission`` then returns the rank's OWN rows only: every other row of
+    ``emission`` is NaN.  A rank whose ``eval_emit`` raises re-raises after the collective; every other rank raises
+    ``RemoteFailure``; no rank's groups change.  Without a process group a sampler with ``world > 1`` is refused."""
+    world = getattr(sampler, "world", 1)
+    if process_group is None and world > 1:
         raise NotImplementedError(
-            "update_ray_groups: data parallelism is not implemented -- with world > 1 every rank holds the full index "
-            "vectors, so all ranks must call apply_flags with the SAME flags (one rank's flags, or all-gathered shares)")
+            "update_ray_groups: without a process_group data parallelism is not possible -- with world > 1 every rank holds "
+            "the full index vectors, so all ranks must call apply_flags with the SAME flags (pass process_group=)")
     bs = DEFAULT_BATCH_SIZE if batch_size is None else int(batch_size)
     if bs < 1:
         raise ValueError("update_ray_groups: batch_size must be positive")
     k_val = float(k_val)
+    if process_group is not None:
+        return _update_ray_groups_dp(renderer, sampler, k_val, bs, verbose, return_emission, process_group)
     dev = torch.device(sampler.device)
     on_device = dev.type == "cuda"
     all_rows = sampler.uncert_data_idxs
@@ -280,8 +484,7 @@ def update_ray_groups(renderer, sampler, k_val: float, batch_size: Optional[int]
     if on_device:
         stats_dev = store[n_pad:].view(torch.int64)
         stats_dev.copy_(_identity())
-    was_training = renderer.training
-    finetune = was_training and getattr(renderer, "forward", None) == getattr(renderer, "forward_finetune", None)
+    was_training, finetune = _mode_of(renderer)
     renderer.eval()
     try:
         for a in range(0, n, bs):
@@ -295,8 +498,7 @@ def update_ray_groups(renderer, sampler, k_val: float, batch_size: Optional[int]
             if return_emission:
                 emission[a:a + len(rows)].copy_(e)
     finally:
-        if was_training:
-            renderer.train(True, finetune=True) if finetune else renderer.train(True)
+        _restore_mode(renderer, was_training, finetune)
     if on_device and all_rows.is_cuda:
         stats = apply_flags(sampler, flags, stats_dev)
         stats.pop("totals")
@@ -310,12 +512,97 @@ def update_ray_groups(renderer, sampler, k_val: float, batch_size: Optional[int]
             stats = _decide_torch(torch.empty(0, 3), k_val)[1]
         apply_flags(sampler, flags)
     if verbose:
-        # pdra.py:912-925; the reference prints the three pairs only for a non-empty selection
-        if n:
-            print("emission(max, min):", stats["max_all"], stats["min_all"])
-        if stats["n_set"]:
-            print("emission_uncert_masks(max, min):", stats["max_set"], stats["min_set"])
-        if stats["n_clear"]:
-            print("emission_cert_masks(max, min):", stats["max_clear"], stats["min_clear"])
-        print("[NEW MASK UPDATE]\n" + _stats_line(sampler))
+        _print_after(sampler, n, stats)
+    return RegroupReport(k_val, before[0], before[1], sampler.uncert_data_num, sampler.cert_data_num, stats, flags, emission)
+
+
+_TAIL_WORDS = _STATS_WORDS + 2 + 1              # what a rank reads back: merged record, totals, failure count
+
+
+def _update_ray_groups_dp(renderer, sampler, k_val, bs, verbose, return_emission, process_group) -> RegroupReport:
+    import torch.distributed as dist
+    rank, world = getattr(sampler, "rank", 0), getattr(sampler, "world", 1)
+    if dist.get_world_size(process_group) != world or dist.get_rank(process_group) != rank:
+        raise ValueError(f"update_ray_groups: the sampler is rank {rank} of {world}, the process group says rank "
+                         f"{dist.get_rank(process_group)} of {dist.get_world_size(process_group)}")
+    bs = (bs + 63) // 64 * 64                    # every chunk starts on a word
+    dev = torch.device(sampler.device)
+    on_device = dev.type == "cuda"
+    all_rows = sampler.uncert_data_idxs
+    n = len(all_rows)
+    nw = n_words(n)
+    lo, hi = ray_share(n, rank, world)
+    before = (sampler.uncert_data_num, sampler.cert_data_num)
+    if verbose:
+        print("[PREV]\n" + _stats_line(sampler) + f"\ncurr k_val: {k_val}")
+    emission = torch.full((n, 3), float("nan"), dtype=torch.float32, device=dev) if return_emission else None
+    rec_bytes = 8 * _STATS_WORDS
+    if on_device:
+        # int64: [nw flag words | world records | merged record | totals | failures], zero outside what this rank owns
+        buf = torch.zeros(nw + _STATS_WORDS * world + _TAIL_WORDS, dtype=torch.int64, device=dev)
+        words, parts, tail = buf[:nw], buf[nw:nw + _STATS_WORDS * world], buf[nw + _STATS_WORDS * world:]
+        mine = parts[_STATS_WORDS * rank:_STATS_WORDS * (rank + 1)]
+        mine.copy_(_identity()[:_STATS_WORDS])
+    else:
+        # uint8: [n flags | world records | world failure bytes]
+        buf = torch.zeros(n + (rec_bytes + 1) * world, dtype=torch.uint8)
+    stats, error = None, None
+    was_training, finetune = _mode_of(renderer)
+    renderer.eval()
+    try:
+        for a in range(lo, hi, bs):
+            b = min(hi, a + bs)
+            e = renderer.eval_emit(**_chunk_rays(sampler, all_rows[a:b], dev))
+            if on_device:
+                decide_bits(e, k_val, words[a // 64:n_words(b)], mine)
+            else:
+                buf[a:b], part = _decide_torch(e, k_val)
+                stats = _merge(stats, part)
+            if return_emission:
+                emission[a:b].copy_(e)
+    except Exception as exc:                     # (joins the collective below, then raises)
+        error = exc
+    finally:
+        _restore_mode(renderer, was_training, finetune)
+    if on_device:
+        if error is not None:
+            tail[-1:].fill_(1)
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=process_group)
+        if error is not None:
+            raise error
+        merge_stats(parts, world, tail)
+        if all_rows.is_cuda:
+            host = _partition_into_sampler(sampler, words, True, tail)
+            flags = unpack_flags(words, n)
+        else:
+            # a CPU home: the unpacked flags travel in front of the tail, in the same copy, to the existing filter lines
+            n_pad = (n + 7) // 8 * 8
+            store = torch.empty(n_pad + 8 * _TAIL_WORDS, dtype=torch.uint8, device=dev)
+            flags = unpack_flags(words, n, store[:n]).view(torch.bool)
+            store[n_pad:].view(torch.int64).copy_(tail)
+            host_all = store.cpu()
+            host = host_all[n_pad:].view(torch.int64).numpy()
+            _raise_if_failed(int(host[-1]))
+            sampler.filter(host_all[:n].view(torch.bool))
+        stats = _parse_stats(host)
+    else:
+        if stats is None:
+            stats = _decide_torch(torch.empty(0, 3), k_val)[1]
+        at = n + rec_bytes * rank
+        rec = _lib.EsrRegroupStats(*(stats[k] for k in STAT_KEYS))
+        buf[at:at + rec_bytes] = torch.frombuffer(bytearray(bytes(rec)), dtype=torch.uint8)
+        buf[n + rec_bytes * world + rank] = int(error is not None)
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=process_group)
+        if error is not None:
+            raise error
+        _raise_if_failed(int(buf[n + rec_bytes * world:].sum()))
+        stats = None
+        for r in range(world):
+            rec = _lib.EsrRegroupStats.from_buffer_copy(buf[n + rec_bytes * r:n + rec_bytes * (r + 1)].numpy().tobytes())
+            stats = _merge(stats, {k: getattr(rec, k) for k in STAT_KEYS})
+        flags = buf[:n].view(torch.bool)
+        apply_flags(sampler, flags)
+    stats.pop("totals", None)
+    if verbose:
+        _print_after(sampler, n, stats)
     return RegroupReport(k_val, before[0], before[1], sampler.uncert_data_num, sampler.cert_data_num, stats, flags, emission)

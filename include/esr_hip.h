@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 37
+#define ESR_ABI_VERSION 38
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -1442,7 +1442,7 @@ typedef struct esr_regroup_stats_t {
  * the NaN and NaN > k is false).  accumulate == 0: *stats is overwritten; accumulate != 0: the call merges into what
  * *stats holds (chunk by chunk over one flag vector, no [n,3] buffer).  Counts, minima and maxima are exact and do not
  * depend on the order of arrival.
- * All three entries of this section: n == 0 is success and touches no pointer; n >= 2^31 is ESR_ECAP; a NULL or
+ * All entries of this section: n == 0 is success and touches no pointer; n >= 2^31 is ESR_ECAP; a NULL or
  * misaligned pointer is ESR_EINVAL; everything is enqueued on `stream` and nothing waits on the host.
  */
 int esr_emit_decide(const float *emission, int64_t n, float k_val, uint8_t *flags, esr_regroup_stats_t *stats,
@@ -1463,6 +1463,36 @@ int esr_flag_scan(const uint8_t *flags, int64_t n, int64_t *block_offsets, int64
  */
 int esr_index_partition(const int64_t *rows, const uint8_t *flags, const int64_t *block_offsets, int64_t n,
                         int64_t *set_out, int64_t *clear_out, void *stream);
+
+/*
+ * The same flags as packed 64-bit words, for a re-split under data parallelism (esr_nerf_amd/csrc/regroup_dp.hip).  Packed
+ * format: bit b of word w is the flag of ray 64 w + b, bit 0 the least significant; the bits at and above n in the last word
+ * are 0; words u64 [ceil(n / 64)], 8-byte aligned.  Shares of a flag vector that are cut at word boundaries combine under an
+ * integer SUM all-reduce of the words (zero outside a rank's share).
+ *
+ * esr_emit_decide_bits: the decision and the statistics of esr_emit_decide (the same comparison, NaN rule, counts, minima and
+ * maxima, the same `accumulate`), written as ceil(n / 64) WHOLE words, one wave ballot each, instead of n bytes.
+ */
+int esr_emit_decide_bits(const float *emission, int64_t n, float k_val, uint64_t *words, esr_regroup_stats_t *stats,
+                         int accumulate, void *stream);
+/* flags u8 [n] (any alignment) -> words: a non-zero byte is a set bit.  Writes ceil(n / 64) whole words, the tail clear. */
+int esr_flags_pack(const uint8_t *flags, int64_t n, uint64_t *words, void *stream);
+/* words -> flags u8 [n]: exactly 0 or 1 per byte */
+int esr_flags_unpack(const uint64_t *words, int64_t n, uint8_t *flags, void *stream);
+/*
+ * esr_flag_scan on packed words: block_offsets and totals mean what they mean there (a tile is ESR_PARTITION_BLOCK flags =
+ * 16 words, counts are popcounts), so either form feeds either partition's offsets.
+ */
+int esr_flag_scan_bits(const uint64_t *words, int64_t n, int64_t *block_offsets, int64_t *totals, void *stream);
+/* esr_index_partition on packed words: the same stable two-way partition, the same rule for a NULL output. */
+int esr_index_partition_bits(const int64_t *rows, const uint64_t *words, const int64_t *block_offsets, int64_t n,
+                             int64_t *set_out, int64_t *clear_out, void *stream);
+/*
+ * *out = the merge of parts [n_parts] (DEVICE memory, records as esr_emit_decide leaves them): counts are added, minima and
+ * maxima are taken in esr_emit_decide's total order (-0.0 below +0.0), a group that is empty in every part keeps +inf / -inf.
+ * One launch of one wave; `out` may be one of the parts.  n_parts == 0 is success and touches no pointer.
+ */
+int esr_regroup_stats_merge(const esr_regroup_stats_t *parts, int64_t n_parts, esr_regroup_stats_t *out, void *stream);
 
 #ifdef __cplusplus
 }
