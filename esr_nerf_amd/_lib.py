@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libesr_hip.so")
 # developer experiments only (python -m esr_nerf_amd.build --variant builds alternative libraries; tools/ab_env.sh times them
 # side by side on one box)
 LIB_PATH = os.environ.get("ESR_LIB_PATH", LIB_PATH)
-ABI_VERSION = 38
+ABI_VERSION = 39
 _lib = None
 
 
@@ -194,9 +194,8 @@ EXPORTS = [
     "esr_camera_rays", "esr_camera_batch", "esr_camera_bounds", "esr_ray_filter_cameras",
     "esr_grid_resample", "esr_maxpool3d", "esr_nonempty_mask", "esr_density_bounds",
     "esr_cc_link", "esr_cc_flatten", "esr_cc_face_labels", "esr_cc_stats",
-    "esr_emit_decide", "esr_flag_scan", "esr_index_partition",
-    "esr_emit_decide_bits", "esr_flags_pack", "esr_flags_unpack", "esr_flag_scan_bits", "esr_index_partition_bits",
-    "esr_regroup_stats_merge",
+    "esr_emit_decide", "esr_emit_decide_bits", "esr_flags_pack", "esr_flags_unpack", "esr_flag_scan_bits",
+    "esr_index_partition_bits", "esr_regroup_stats_merge",
 ]
 
 # full ctypes signatures (argument conversion checked on every call) of the entries that declare them
@@ -235,8 +234,6 @@ SIGNATURES = {
                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p]),
     "esr_emit_decide": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "esr_flag_scan": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "esr_index_partition": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "esr_emit_decide_bits": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "esr_flags_pack": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "esr_flags_unpack": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),

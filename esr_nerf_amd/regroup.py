@@ -1,23 +1,33 @@
 """PDRA's ray re-split: which uncertain rays stay uncertain -- ``update_ray_groups`` of the reference's PDRA trainer
 (app/fine/pdra.py:882-932) with ``RayGroupManager.filter`` (utils2/utils.py:234-267) -- over the kernels of
-esr_nerf_amd/csrc/regroup.hip and, for the re-split under data parallelism, csrc/regroup_dp.hip.
+esr_nerf_amd/csrc/regroup.hip.
 
 ``decide``             emission [n, 3] -> one flag per ray (``max_c emission > k_val``) and the statistics the reference
-                       prints, in one launch; chunk after chunk into one flag vector and one statistics record
-``partition``          rows, flags -> ``(rows[flags], rows[~flags])``, both in input order (count, scan, scatter)
+                       prints, in one launch; chunk after chunk into one flag vector and one statistics record;
+                       ``decide_bits``: the same into 64-bit words, for chunks that start on a multiple of 64 rays
+``pack_flags`` / ``unpack_flags``   byte flags <-> words; the scan and the partition run on words only
+``partition``          rows, flags -> ``(rows[flags], rows[~flags])``, both in input order (pack, count, scan, scatter)
 ``apply_flags``        what ``sampler.filter(flags)`` does, for a ``RayGroupManager`` or a ``CameraRayGroupManager``; byte flags
-                       or (``packed=True``) 64-bit words
-``ray_share``          the rays of the uncertain group a rank decides; ``pack_flags`` / ``unpack_flags``: bytes <-> words
-``update_ray_groups``  the trainer's method: ``eval_emit`` over the uncertain group in chunks, ``decide`` per chunk,
-                       ``apply_flags`` once, the reference's printed lines -> ``RegroupReport``
+                       (packed first) or, with ``packed=True``, the words themselves
+``ray_share``          the rays of the uncertain group a rank decides
+``update_ray_groups``  the trainer's method: ``eval_emit`` over the uncertain group in chunks, the decision per chunk, the
+                       partition once, the reference's printed lines -> ``RegroupReport``
 
 A PDRA trainer calls ``update_ray_groups(self.renderer, self.sampler, self.k_val)`` where the reference calls
 ``self.update_ray_groups(self.k_val)`` (pdra.py:219 and :372).
 
+One driver.  ``update_ray_groups`` lays out ONE int64 device buffer ``[W flag words | world statistics records | merged record
+| totals | failures]``, decides chunk after chunk, and then runs one path on the words: ``esr_regroup_stats_merge`` (world > 1),
+``esr_flag_scan_bits``, ONE read-back, exact-size allocation, ``esr_index_partition_bits``.  Without a process group it is the
+case world = 1 with the share ``(0, n)``: chunks are exactly ``batch_size`` rays and may start at any ray, so each is decided
+into a byte vector (``esr_emit_decide``) that ONE ``esr_flags_pack`` turns into the words, and the record is decided straight
+into the merged slot.
+
 Host read-backs.  ``update_ray_groups`` reads back once per call.  For a sampler whose index vectors live on the device
-these are 64 bytes (the statistics and the two totals the allocation of the new vectors needs); a ``data_preload: cpu``
-sampler keeps its index vectors on the host, so the flags travel in the same copy, in front of the statistics, and the
-existing ``filter`` lines run on them.  (``eval_emit`` itself reads its march plan back per chunk; that is the engine's.)
+these are 72 bytes (the statistics record, the two totals the allocation of the new vectors needs, and the failure count,
+which is 0 without a process group); a ``data_preload: cpu`` sampler keeps its index vectors on the host, so the byte flags
+travel in the same copy, in front of those 72 bytes, and the existing ``filter`` lines run on them.  (``eval_emit`` itself
+reads its march plan back per chunk; that is the engine's.)
 
 Fine-tune mode.  The mode is put back as ``relight.EditRaySelector`` does, with ``renderer.train(True, finetune=True)``, and
 ``ESRNeRF.train`` then freezes a NEW copy of the current ``emo_color`` as ``emit_color`` (esrnerf.py:218-239): a re-split in
@@ -29,18 +39,18 @@ Data parallelism.  The groups change ONLY through ``apply_flags``, which is a de
 flags each rank decided for itself on the same ray (a ray on the boundary may be decided differently by two ranks, and the
 index vectors would diverge).  ``update_ray_groups(..., process_group=pg)`` does it so: rank r evaluates ``eval_emit`` on its
 share ``ray_share(n, r, world)`` of the uncertain group only -- shares are disjoint and start on multiples of 64 rays -- and
-decides it into its 64-bit words (one bit per ray, ``esr_emit_decide_bits``: a wave's ballot) of ONE int64 device buffer
-``[W flag words | world statistics records | merged record | totals | failures]`` that is zero outside what the rank owns.
-ONE ``all_reduce(SUM)`` of that buffer is then the union of the decisions and the gather of the records (zero plus bits is
-bits, for the float fields too) and carries the failure count; ``esr_regroup_stats_merge``, ``esr_flag_scan_bits`` and
-``esr_index_partition_bits`` follow on the words, and the ONE read-back (72 bytes: record, totals, failures) precedes the
-allocation.  No ray is decided by two ranks, so nothing depends on two ranks agreeing to the last bit.  A rank whose
-``eval_emit`` raises still joins the collective with its failure word set, and EVERY rank raises, its groups untouched.
-``update_ray_groups`` on a sampler with ``world > 1`` and no process group raises ``NotImplementedError``.
+decides it into its 64-bit words (one bit per ray, ``esr_emit_decide_bits``: a wave's ballot) and its record of the buffer
+above, which is zero outside what the rank owns.  ONE ``all_reduce(SUM)`` of that buffer is then the union of the decisions
+and the gather of the records (zero plus bits is bits, for the float fields too) and carries the failure count; the word
+path follows, and the ONE read-back (72 bytes: record, totals, failures) precedes the allocation.  No ray is decided by two
+ranks, so nothing depends on two ranks agreeing to the last bit.  A rank whose ``eval_emit`` raises still joins the
+collective with its failure word set, and EVERY rank raises, its groups untouched.  ``update_ray_groups`` on a sampler with
+``world > 1`` and no process group raises ``NotImplementedError``.
 
 There is no CPU kernel: ``decide`` and ``partition`` raise on CPU tensors.  ``update_ray_groups`` with a renderer on the CPU
-(a stub in the tests) takes the reference's torch statements for the decision, under a process group with the same shares:
-one SUM all-reduce of a zero-filled uint8 vector (the flags, one byte each, then every rank's record and failure byte).
+(a stub in the tests) takes the reference's torch statements for the decision, into one zero-filled uint8 vector (the flags,
+one byte each, then every rank's record and failure byte); under a process group, with the same shares, one SUM all-reduce
+of that vector.
 """
 from __future__ import annotations
 
@@ -102,55 +112,44 @@ def _parse_stats(host) -> Dict[str, float]:
     return out
 
 
-@torch.no_grad()
-def decide(emission: torch.Tensor, k_val: float, flags: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None):
-    """emission [n, 3] float32 device tensor -> ``(flags, stats)``: ``flags`` [n] bool (``max_c emission > k_val`` as a
-    binary32 comparison; a ray with a NaN channel is not set), written into the given vector (bool or uint8, e.g. a slice
-    of a longer one) or a new one; ``stats`` the device buffer of ``new_stats`` -- a given one is MERGED into (chunk after
-    chunk), without one a new record is started.  One launch on the current stream, not waited for; ``read_stats`` reads."""
-    _need_device("decide", emission)
-    if emission.dim() != 2 or emission.shape[1] != 3 or emission.dtype != torch.float32:
-        raise ValueError(f"decide: emission is [n, 3] float32, got {emission.dtype} {tuple(emission.shape)}")
-    dev = emission.device
-    e = emission.contiguous()
-    n = int(e.shape[0])
-    with torch.cuda.device(dev):
-        if flags is None:
-            flags = torch.empty(n, dtype=torch.bool, device=dev)
-        if len(flags) != n or flags.device != dev:
-            raise ValueError(f"decide: {n} rays on {dev}, flags {tuple(flags.shape)} on {flags.device}")
-        accumulate = stats is not None
-        if stats is None:
-            stats = new_stats(dev)
-            if n == 0:                                   # (the entry point touches nothing for n == 0)
-                stats.copy_(_identity().to(dev))
-        _lib.check(_lib.lib().esr_emit_decide(_lib.ptr(e), n, float(k_val), _lib.ptr(_u8(flags)), _lib.ptr(stats),
-                                              int(accumulate), _lib.stream_ptr(dev)), "esr_emit_decide")
-    return (flags if flags.dtype == torch.bool else flags.view(torch.bool)), stats
-
-
 def _identity() -> torch.Tensor:
     inf = float("inf")
     rec = _lib.EsrRegroupStats(0, 0, 0, inf, -inf, inf, -inf, inf, -inf)
     return torch.frombuffer(bytearray(bytes(rec)) + bytearray(16), dtype=torch.int64).clone()
 
 
-def _scan(flags_u8: torch.Tensor, totals: torch.Tensor) -> torch.Tensor:
-    dev = flags_u8.device
-    n = int(flags_u8.numel())
-    off = torch.empty((n + _lib.PARTITION_BLOCK - 1) // _lib.PARTITION_BLOCK, dtype=torch.int64, device=dev)
-    if n == 0:
-        totals.zero_()
-    _lib.check(_lib.lib().esr_flag_scan(_lib.ptr(flags_u8), n, _lib.ptr(off), _lib.ptr(totals), _lib.stream_ptr(dev)),
-               "esr_flag_scan")
-    return off
+def _decide_setup(what: str, emission: torch.Tensor, stats: Optional[torch.Tensor]):
+    """What ``decide`` and ``decide_bits`` share: the checks on ``emission`` and the statistics record -- a given one is
+    merged into, without one a new record is started -> ``(emission, n, stats, accumulate)``"""
+    _need_device(what, emission)
+    if emission.dim() != 2 or emission.shape[1] != 3 or emission.dtype != torch.float32:
+        raise ValueError(f"{what}: emission is [n, 3] float32, got {emission.dtype} {tuple(emission.shape)}")
+    n = int(emission.shape[0])
+    accumulate = stats is not None
+    if stats is None:
+        with torch.cuda.device(emission.device):
+            stats = new_stats(emission.device)
+            if n == 0:                                   # (the entry points touch nothing for n == 0)
+                stats.copy_(_identity().to(emission.device))
+    return emission.contiguous(), n, stats, int(accumulate)
 
 
-def _scatter(rows, flags_u8, off, set_out, clear_out):
-    dev = rows.device
-    _lib.check(_lib.lib().esr_index_partition(_lib.ptr(rows), _lib.ptr(flags_u8), _lib.ptr(off), int(rows.numel()),
-                                              _lib.ptr(set_out), _lib.ptr(clear_out), _lib.stream_ptr(dev)),
-               "esr_index_partition")
+@torch.no_grad()
+def decide(emission: torch.Tensor, k_val: float, flags: Optional[torch.Tensor] = None, stats: Optional[torch.Tensor] = None):
+    """emission [n, 3] float32 device tensor -> ``(flags, stats)``: ``flags`` [n] bool (``max_c emission > k_val`` as a
+    binary32 comparison; a ray with a NaN channel is not set), written into the given vector (bool or uint8, e.g. a slice
+    of a longer one) or a new one; ``stats`` the device buffer of ``new_stats`` -- a given one is MERGED into (chunk after
+    chunk), without one a new record is started.  One launch on the current stream, not waited for; ``read_stats`` reads."""
+    e, n, stats, accumulate = _decide_setup("decide", emission, stats)
+    dev = e.device
+    with torch.cuda.device(dev):
+        if flags is None:
+            flags = torch.empty(n, dtype=torch.bool, device=dev)
+        if len(flags) != n or flags.device != dev:
+            raise ValueError(f"decide: {n} rays on {dev}, flags {tuple(flags.shape)} on {flags.device}")
+        _lib.check(_lib.lib().esr_emit_decide(_lib.ptr(e), n, float(k_val), _lib.ptr(_u8(flags)), _lib.ptr(stats), accumulate,
+                                              _lib.stream_ptr(dev)), "esr_emit_decide")
+    return (flags if flags.dtype == torch.bool else flags.view(torch.bool)), stats
 
 
 def _check_rows(what, rows, flags):
@@ -161,19 +160,21 @@ def _check_rows(what, rows, flags):
 
 @torch.no_grad()
 def partition(rows: torch.Tensor, flags: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    """``(rows[flags], rows[~flags])`` for an int64 device vector and its bool / uint8 flags, both in input order.  Reads the
-    two totals back (the results are allocated at their exact sizes)."""
+    """``(rows[flags], rows[~flags])`` for an int64 device vector and its bool / uint8 flags (a non-zero byte is a set
+    flag), both in input order: ``pack_flags``, then the scan and the partition on the words.  Reads the two totals back (the
+    results are allocated at their exact sizes)."""
     _need_device("partition", rows, flags)
     _check_rows("partition", rows, flags)
     dev = rows.device
-    f, r = _u8(flags), rows.contiguous()
+    n, r = len(rows), rows.contiguous()
     with torch.cuda.device(dev):
+        words = pack_flags(flags)
         totals = torch.empty(2, dtype=torch.int64, device=dev)
-        off = _scan(f, totals)
+        off = _scan(words, n, totals)
         n_set, n_clear = totals.tolist()
         set_rows = torch.empty(n_set, dtype=torch.int64, device=dev)
         clear_rows = torch.empty(n_clear, dtype=torch.int64, device=dev)
-        _scatter(r, f, off, set_rows, clear_rows)
+        _scatter(r, words, off, set_rows, clear_rows)
     return set_rows, clear_rows
 
 
@@ -256,23 +257,14 @@ def decide_bits(emission: torch.Tensor, k_val: float, words: Optional[torch.Tens
     """``decide`` with the flags as packed words: emission [n, 3] -> ``(words, stats)``, ``words`` int64 [ceil(n / 64)] (a
     given vector may be a slice of a longer one: a chunk that starts on a multiple of 64 rays starts on a word), ``stats`` as
     ``decide`` treats it.  One launch, not waited for."""
-    _need_device("decide_bits", emission)
-    if emission.dim() != 2 or emission.shape[1] != 3 or emission.dtype != torch.float32:
-        raise ValueError(f"decide_bits: emission is [n, 3] float32, got {emission.dtype} {tuple(emission.shape)}")
-    dev = emission.device
-    e = emission.contiguous()
-    n = int(e.shape[0])
+    e, n, stats, accumulate = _decide_setup("decide_bits", emission, stats)
+    dev = e.device
     with torch.cuda.device(dev):
         if words is None:
             words = torch.empty(n_words(n), dtype=torch.int64, device=dev)
         _check_words("decide_bits", words, n)
-        accumulate = stats is not None
-        if stats is None:
-            stats = new_stats(dev)
-            if n == 0:
-                stats.copy_(_identity().to(dev))
-        _lib.check(_lib.lib().esr_emit_decide_bits(_lib.ptr(e), n, float(k_val), _lib.ptr(words), _lib.ptr(stats),
-                                                   int(accumulate), _lib.stream_ptr(dev)), "esr_emit_decide_bits")
+        _lib.check(_lib.lib().esr_emit_decide_bits(_lib.ptr(e), n, float(k_val), _lib.ptr(words), _lib.ptr(stats), accumulate,
+                                                   _lib.stream_ptr(dev)), "esr_emit_decide_bits")
     return words, stats
 
 
@@ -287,7 +279,7 @@ def merge_stats(parts: torch.Tensor, n_parts: int, out: torch.Tensor):
                                                       _lib.stream_ptr(parts.device)), "esr_regroup_stats_merge")
 
 
-def _scan_bits(words: torch.Tensor, n: int, totals: torch.Tensor) -> torch.Tensor:
+def _scan(words: torch.Tensor, n: int, totals: torch.Tensor) -> torch.Tensor:
     dev = words.device
     off = torch.empty((n + _lib.PARTITION_BLOCK - 1) // _lib.PARTITION_BLOCK, dtype=torch.int64, device=dev)
     if n == 0:
@@ -297,7 +289,7 @@ def _scan_bits(words: torch.Tensor, n: int, totals: torch.Tensor) -> torch.Tenso
     return off
 
 
-def _scatter_bits(rows, words, off, set_out, clear_out):
+def _scatter(rows, words, off, set_out, clear_out):
     dev = rows.device
     _lib.check(_lib.lib().esr_index_partition_bits(_lib.ptr(rows), _lib.ptr(words), _lib.ptr(off), int(rows.numel()),
                                                    _lib.ptr(set_out), _lib.ptr(clear_out), _lib.stream_ptr(dev)),
@@ -314,15 +306,15 @@ def _raise_if_failed(n_failed: int):
                             f"groups were changed")
 
 
-def _partition_into_sampler(sampler, f: torch.Tensor, packed: bool, buf: torch.Tensor):
-    """Index vectors on the device: scan into the totals of ``buf`` (int64: record, totals, and for a re-split under a
-    process group the failure count), ONE read-back of ``buf``, exact-size allocation, the partition -> ``buf`` on the host"""
+def _partition_into_sampler(sampler, words: torch.Tensor, buf: torch.Tensor):
+    """Index vectors on the device: scan of the packed flags into the totals of ``buf`` (int64: record, totals, and for
+    ``update_ray_groups`` the failure count), ONE read-back of ``buf``, exact-size allocation, the partition -> ``buf`` on the
+    host"""
     rows, old = sampler.uncert_data_idxs, sampler.cert_data_idxs
     dev = rows.device
     n = len(rows)
     with torch.cuda.device(dev):
-        totals = buf[_STATS_WORDS:_STATS_WORDS + 2]
-        off = _scan_bits(f, n, totals) if packed else _scan(f, totals)
+        off = _scan(words, n, buf[_STATS_WORDS:_STATS_WORDS + 2])
         host = buf.cpu().numpy()
         if len(host) > _STATS_WORDS + 2:
             _raise_if_failed(int(host[_STATS_WORDS + 2]))
@@ -330,7 +322,7 @@ def _partition_into_sampler(sampler, f: torch.Tensor, packed: bool, buf: torch.T
         new_u = torch.empty(n_set, dtype=torch.int64, device=dev)
         new_c = torch.empty(len(old) + n_clear, dtype=torch.int64, device=dev)
         new_c[:len(old)].copy_(old)
-        (_scatter_bits if packed else _scatter)(rows.contiguous(), f, off, new_u, new_c[len(old):])
+        _scatter(rows.contiguous(), words, off, new_u, new_c[len(old):])
     sampler.uncert_data_idxs, sampler.cert_data_idxs = new_u, new_c
     return host
 
@@ -340,11 +332,12 @@ def apply_flags(sampler, flags: torch.Tensor, stats: Optional[torch.Tensor] = No
                 packed: bool = False) -> Optional[Dict[str, float]]:
     """``sampler.filter(flags)``: a set flag keeps its ray uncertain, a clear one moves it to the END of the certain group;
     ``uncert_batch_st`` and ``cert_batch_st`` stay as they are.  ``flags`` is aligned with the uncertain group's current
-    order: a bool / uint8 vector with one entry per ray, or with ``packed=True`` the int64 vector of ``ceil(n / 64)`` words of
-    ``pack_flags`` (said by the keyword, never guessed from a dtype).  Index vectors on the device: scan, one read-back (of
-    ``stats`` when given, whose last two words take the totals), exact-size allocation, a device copy of the old certain
-    vector, the partition.  A ``data_preload: cpu`` sampler: the existing ``filter`` lines (on unpacked flags).  With
-    ``world > 1`` all ranks must pass the SAME flags (module docstring).  Returns ``read_stats(stats)`` when ``stats`` is given."""
+    order: a bool / uint8 vector with one entry per ray (a non-zero byte is a set flag), or with ``packed=True`` the int64
+    vector of ``ceil(n / 64)`` words of ``pack_flags`` (said by the keyword, never guessed from a dtype).  Index vectors on
+    the device: byte flags are packed, then scan, one read-back (of ``stats`` when given, whose last two words take the
+    totals), exact-size allocation, a device copy of the old certain vector, the partition.  A ``data_preload: cpu`` sampler:
+    the existing ``filter`` lines (on unpacked flags).  With ``world > 1`` all ranks must pass the SAME flags (module
+    docstring).  Returns ``read_stats(stats)`` when ``stats`` is given."""
     rows = sampler.uncert_data_idxs
     if packed:
         _check_words("apply_flags", flags, len(rows))
@@ -359,15 +352,11 @@ def apply_flags(sampler, flags: torch.Tensor, stats: Optional[torch.Tensor] = No
         sampler.filter(flags.view(torch.bool) if flags.dtype == torch.uint8 else flags)
         return host
     _need_device("apply_flags", flags)
-    if packed:
-        if flags.device != rows.device or rows.dtype != torch.int64 or rows.dim() != 1:
-            raise ValueError(f"apply_flags: int64 rows and their words on one device, got {rows.dtype} on {rows.device} and "
-                             f"words on {flags.device}")
-        f = flags
-    else:
-        _check_rows("apply_flags", rows, flags)
-        f = _u8(flags)
-    host = _partition_into_sampler(sampler, f, packed, stats if stats is not None else new_stats(rows.device))
+    if flags.device != rows.device or rows.dtype != torch.int64 or rows.dim() != 1:
+        raise ValueError(f"apply_flags: int64 rows and their flags on one device, got {rows.dtype} {tuple(rows.shape)} on "
+                         f"{rows.device} and flags on {flags.device}")
+    words = flags if packed else pack_flags(flags)
+    host = _partition_into_sampler(sampler, words, stats if stats is not None else new_stats(rows.device))
     return _parse_stats(host) if stats is not None else None
 
 
@@ -441,6 +430,26 @@ def _print_after(sampler, n: int, stats: Dict[str, float]):
     print("[NEW MASK UPDATE]\n" + _stats_line(sampler))
 
 
+_TAIL_WORDS = _STATS_WORDS + 2 + 1              # what a call reads back: merged record, totals, failure count
+_REC_BYTES = 8 * _STATS_WORDS
+
+
+def _all_reduce_host(buf: torch.Tensor, n: int, stats: Dict[str, float], failed: bool, rank: int, world: int, process_group):
+    """The collective of the CPU arm: this rank's record and failure byte go into their slots behind the ``n`` flags of the
+    zero-filled uint8 ``buf``, ONE SUM all-reduce -> ``(the merged statistics, the number of ranks that failed)``"""
+    import torch.distributed as dist
+    recs = n + _REC_BYTES * world
+    rec = _lib.EsrRegroupStats(*(stats[k] for k in STAT_KEYS))
+    buf[n + _REC_BYTES * rank:n + _REC_BYTES * (rank + 1)] = torch.frombuffer(bytearray(bytes(rec)), dtype=torch.uint8)
+    buf[recs + rank] = int(failed)
+    dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=process_group)
+    merged = None
+    for r in range(world):
+        rec = _lib.EsrRegroupStats.from_buffer_copy(buf[n + _REC_BYTES * r:n + _REC_BYTES * (r + 1)].numpy().tobytes())
+        merged = _merge(merged, {k: getattr(rec, k) for k in STAT_KEYS})
+    return merged, int(buf[recs:].sum())
+
+
 @torch.no_grad()
 def update_ray_groups(renderer, sampler, k_val: float, batch_size: Optional[int] = None, verbose: bool = True,
                       return_emission: bool = False, process_group=None) -> RegroupReport:
@@ -448,14 +457,19 @@ def update_ray_groups(renderer, sampler, k_val: float, batch_size: Optional[int]
     ``batch_size`` rays per pass (None: ``DEFAULT_BATCH_SIZE``); a ray stays uncertain iff ``max_c emission > k_val``, all
     others go to the end of the certain group.  The renderer is in ``eval()`` for the duration and gets its mode (train or
     fine-tune) back afterwards, also when ``eval_emit`` raises.  No [n, 3] emission buffer is kept unless
-    ``return_emission``.  ``verbose`` prints the reference's lines.
+    ``return_emission``.  ``verbose`` prints the reference's lines.  ONE read-back: the merged record, the totals and the
+    failure count, 72 bytes with or without a process group (the failure count is then 0).
+
+    Without a process group chunks are exactly ``batch_size`` rays: each is decided into a byte vector (``decide``), which
+    ONE ``pack_flags`` turns into the words of the partition; ``flags`` of the report is that byte vector.
 
     ``process_group`` (a ``torch.distributed`` group of ``sampler.world`` ranks, this one ``sampler.rank``): the re-split
     under data parallelism of the module docstring.  Every rank evaluates only ``ray_share(n, rank, world)``, in chunks of
-    ``batch_size`` rounded up to a multiple of 64; one all-reduce; every rank ends with the same groups, report counts,
-    statistics and ``flags`` (the full vector).  ``return_emission`` then returns the rank's OWN rows only: every other row of
-    ``emission`` is NaN.  A rank whose ``eval_emit`` raises re-raises after the collective; every other rank raises
-    ``RemoteFailure``; no rank's groups change.  Without a process group a sampler with ``world > 1`` is refused."""
+    ``batch_size`` rounded up to a multiple of 64, straight into its words (``decide_bits``); one all-reduce; every rank ends
+    with the same groups, report counts, statistics and ``flags`` (the full vector, from ``unpack_flags``).
+    ``return_emission`` then returns the rank's OWN rows only: every other row of ``emission`` is NaN.  A rank whose
+    ``eval_emit`` raises re-raises after the collective; every other rank raises ``RemoteFailure``; no rank's groups change.
+    Without a process group a sampler with ``world > 1`` is refused."""
     world = getattr(sampler, "world", 1)
     if process_group is None and world > 1:
         raise NotImplementedError(
@@ -465,87 +479,42 @@ def update_ray_groups(renderer, sampler, k_val: float, batch_size: Optional[int]
     if bs < 1:
         raise ValueError("update_ray_groups: batch_size must be positive")
     k_val = float(k_val)
+    rank = 0
     if process_group is not None:
-        return _update_ray_groups_dp(renderer, sampler, k_val, bs, verbose, return_emission, process_group)
+        import torch.distributed as dist
+        rank = getattr(sampler, "rank", 0)
+        if dist.get_world_size(process_group) != world or dist.get_rank(process_group) != rank:
+            raise ValueError(f"update_ray_groups: the sampler is rank {rank} of {world}, the process group says rank "
+                             f"{dist.get_rank(process_group)} of {dist.get_world_size(process_group)}")
+        bs = (bs + 63) // 64 * 64                # every chunk starts on a word
     dev = torch.device(sampler.device)
     on_device = dev.type == "cuda"
     all_rows = sampler.uncert_data_idxs
     n = len(all_rows)
+    nw, n_pad = n_words(n), (n + 7) // 8 * 8
+    lo, hi = ray_share(n, rank, world)           # (0, n) for world = 1
     before = (sampler.uncert_data_num, sampler.cert_data_num)
     if verbose:
         print("[PREV]\n" + _stats_line(sampler) + f"\ncurr k_val: {k_val}")
-    # one device buffer: the flags, then (8-byte aligned) the statistics record and the totals -- a CPU-home sampler
-    # reads all of it back in one copy
-    n_pad = (n + 7) // 8 * 8
-    store = torch.empty(n_pad + 8 * (_STATS_WORDS + 2), dtype=torch.uint8, device=dev)
-    flags = store[:n].view(torch.bool)
-    emission = torch.empty(n, 3, dtype=torch.float32, device=dev) if return_emission else None
-    stats_dev, stats = None, None
+    emission = None
+    if return_emission:
+        emission = (torch.empty(n, 3, dtype=torch.float32, device=dev) if process_group is None else
+                    torch.full((n, 3), float("nan"), dtype=torch.float32, device=dev))
     if on_device:
-        stats_dev = store[n_pad:].view(torch.int64)
-        stats_dev.copy_(_identity())
-    was_training, finetune = _mode_of(renderer)
-    renderer.eval()
-    try:
-        for a in range(0, n, bs):
-            rows = all_rows[a:a + bs]
-            e = renderer.eval_emit(**_chunk_rays(sampler, rows, dev))
-            if on_device:
-                decide(e, k_val, flags[a:a + len(rows)], stats_dev)
-            else:
-                flags[a:a + len(rows)], part = _decide_torch(e, k_val)
-                stats = _merge(stats, part)
-            if return_emission:
-                emission[a:a + len(rows)].copy_(e)
-    finally:
-        _restore_mode(renderer, was_training, finetune)
-    if on_device and all_rows.is_cuda:
-        stats = apply_flags(sampler, flags, stats_dev)
-        stats.pop("totals")
-    elif on_device:
-        host = store.cpu()
-        stats = _parse_stats(host[n_pad:].view(torch.int64).numpy())
-        stats.pop("totals")
-        sampler.filter(host[:n].view(torch.bool))
-    else:
-        if stats is None:
-            stats = _decide_torch(torch.empty(0, 3), k_val)[1]
-        apply_flags(sampler, flags)
-    if verbose:
-        _print_after(sampler, n, stats)
-    return RegroupReport(k_val, before[0], before[1], sampler.uncert_data_num, sampler.cert_data_num, stats, flags, emission)
-
-
-_TAIL_WORDS = _STATS_WORDS + 2 + 1              # what a rank reads back: merged record, totals, failure count
-
-
-def _update_ray_groups_dp(renderer, sampler, k_val, bs, verbose, return_emission, process_group) -> RegroupReport:
-    import torch.distributed as dist
-    rank, world = getattr(sampler, "rank", 0), getattr(sampler, "world", 1)
-    if dist.get_world_size(process_group) != world or dist.get_rank(process_group) != rank:
-        raise ValueError(f"update_ray_groups: the sampler is rank {rank} of {world}, the process group says rank "
-                         f"{dist.get_rank(process_group)} of {dist.get_world_size(process_group)}")
-    bs = (bs + 63) // 64 * 64                    # every chunk starts on a word
-    dev = torch.device(sampler.device)
-    on_device = dev.type == "cuda"
-    all_rows = sampler.uncert_data_idxs
-    n = len(all_rows)
-    nw = n_words(n)
-    lo, hi = ray_share(n, rank, world)
-    before = (sampler.uncert_data_num, sampler.cert_data_num)
-    if verbose:
-        print("[PREV]\n" + _stats_line(sampler) + f"\ncurr k_val: {k_val}")
-    emission = torch.full((n, 3), float("nan"), dtype=torch.float32, device=dev) if return_emission else None
-    rec_bytes = 8 * _STATS_WORDS
-    if on_device:
-        # int64: [nw flag words | world records | merged record | totals | failures], zero outside what this rank owns
-        buf = torch.zeros(nw + _STATS_WORDS * world + _TAIL_WORDS, dtype=torch.int64, device=dev)
-        words, parts, tail = buf[:nw], buf[nw:nw + _STATS_WORDS * world], buf[nw + _STATS_WORDS * world:]
-        mine = parts[_STATS_WORDS * rank:_STATS_WORDS * (rank + 1)]
+        # int64: [nw flag words | world records | merged record | totals | failures], zero outside what this rank owns; the
+        # one rank of world = 1 decides its record straight into the merged slot
+        n_parts = world if world > 1 else 0
+        buf = torch.zeros(nw + _STATS_WORDS * n_parts + _TAIL_WORDS, dtype=torch.int64, device=dev)
+        words, parts, tail = buf[:nw], buf[nw:nw + _STATS_WORDS * n_parts], buf[nw + _STATS_WORDS * n_parts:]
+        mine = parts[_STATS_WORDS * rank:_STATS_WORDS * (rank + 1)] if n_parts else tail[:_STATS_WORDS]
         mine.copy_(_identity()[:_STATS_WORDS])
+        # uint8: the byte flags, with room behind them (8-byte aligned) for the tail -- a CPU-home sampler reads both back
+        # in one copy
+        store = torch.empty(n_pad + 8 * _TAIL_WORDS, dtype=torch.uint8, device=dev)
     else:
         # uint8: [n flags | world records | world failure bytes]
-        buf = torch.zeros(n + (rec_bytes + 1) * world, dtype=torch.uint8)
+        store = torch.zeros(n + (_REC_BYTES + 1) * world, dtype=torch.uint8)
+    flags = store[:n].view(torch.bool)
     stats, error = None, None
     was_training, finetune = _mode_of(renderer)
     renderer.eval()
@@ -553,56 +522,53 @@ def _update_ray_groups_dp(renderer, sampler, k_val, bs, verbose, return_emission
         for a in range(lo, hi, bs):
             b = min(hi, a + bs)
             e = renderer.eval_emit(**_chunk_rays(sampler, all_rows[a:b], dev))
-            if on_device:
-                decide_bits(e, k_val, words[a // 64:n_words(b)], mine)
-            else:
-                buf[a:b], part = _decide_torch(e, k_val)
+            if not on_device:
+                flags[a:b], part = _decide_torch(e, k_val)
                 stats = _merge(stats, part)
+            elif process_group is None:
+                decide(e, k_val, flags[a:b], mine)
+            else:
+                decide_bits(e, k_val, words[a // 64:n_words(b)], mine)
             if return_emission:
                 emission[a:b].copy_(e)
-    except Exception as exc:                     # (joins the collective below, then raises)
-        error = exc
+    except Exception as exc:
+        if process_group is None:
+            raise
+        error = exc                              # (joins the collective below, then raises)
     finally:
         _restore_mode(renderer, was_training, finetune)
     if on_device:
-        if error is not None:
-            tail[-1:].fill_(1)
-        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=process_group)
-        if error is not None:
-            raise error
-        merge_stats(parts, world, tail)
-        if all_rows.is_cuda:
-            host = _partition_into_sampler(sampler, words, True, tail)
-            flags = unpack_flags(words, n)
+        if process_group is not None:
+            if error is not None:
+                tail[-1:].fill_(1)
+            dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=process_group)
+            if error is not None:
+                raise error
+            unpack_flags(words, n, flags)
         else:
-            # a CPU home: the unpacked flags travel in front of the tail, in the same copy, to the existing filter lines
-            n_pad = (n + 7) // 8 * 8
-            store = torch.empty(n_pad + 8 * _TAIL_WORDS, dtype=torch.uint8, device=dev)
-            flags = unpack_flags(words, n, store[:n]).view(torch.bool)
+            pack_flags(flags, words)
+        if n_parts:
+            merge_stats(parts, world, tail)
+        if all_rows.is_cuda:
+            host = _partition_into_sampler(sampler, words, tail)
+        else:
+            # a CPU home: the byte flags travel in front of the tail, in the same copy, to the existing filter lines
             store[n_pad:].view(torch.int64).copy_(tail)
             host_all = store.cpu()
             host = host_all[n_pad:].view(torch.int64).numpy()
             _raise_if_failed(int(host[-1]))
             sampler.filter(host_all[:n].view(torch.bool))
         stats = _parse_stats(host)
+        stats.pop("totals")
     else:
         if stats is None:
             stats = _decide_torch(torch.empty(0, 3), k_val)[1]
-        at = n + rec_bytes * rank
-        rec = _lib.EsrRegroupStats(*(stats[k] for k in STAT_KEYS))
-        buf[at:at + rec_bytes] = torch.frombuffer(bytearray(bytes(rec)), dtype=torch.uint8)
-        buf[n + rec_bytes * world + rank] = int(error is not None)
-        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=process_group)
-        if error is not None:
-            raise error
-        _raise_if_failed(int(buf[n + rec_bytes * world:].sum()))
-        stats = None
-        for r in range(world):
-            rec = _lib.EsrRegroupStats.from_buffer_copy(buf[n + rec_bytes * r:n + rec_bytes * (r + 1)].numpy().tobytes())
-            stats = _merge(stats, {k: getattr(rec, k) for k in STAT_KEYS})
-        flags = buf[:n].view(torch.bool)
+        if process_group is not None:
+            stats, n_failed = _all_reduce_host(store, n, stats, error is not None, rank, world, process_group)
+            if error is not None:
+                raise error
+            _raise_if_failed(n_failed)
         apply_flags(sampler, flags)
-    stats.pop("totals", None)
     if verbose:
         _print_after(sampler, n, stats)
     return RegroupReport(k_val, before[0], before[1], sampler.uncert_data_num, sampler.cert_data_num, stats, flags, emission)

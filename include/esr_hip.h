@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 38
+#define ESR_ABI_VERSION 39
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -1421,11 +1421,11 @@ int esr_cc_stats(const double *vertices, const int64_t *triangles, const int32_t
                  void *stream);
 
 /* ------------------------------------------------------------------------- *
- * P. PDRA ray re-split (update_ray_groups): decide, count, partition
+ * P. PDRA ray re-split (update_ray_groups): decide, pack, count, partition
  * ------------------------------------------------------------------------- */
 
-#define ESR_PARTITION_BLOCK 1024      /* flags (rows) per tile of esr_flag_scan / esr_index_partition                       */
-#define ESR_PARTITION_SCAN_TILE 1024  /* tile counts per trip of the one-block scan launch of esr_flag_scan                 */
+#define ESR_PARTITION_BLOCK 1024      /* flags (rows) per tile of esr_flag_scan_bits / esr_index_partition_bits: 16 words   */
+#define ESR_PARTITION_SCAN_TILE 1024  /* tile counts per trip of the one-block scan launch of esr_flag_scan_bits            */
 
 /* What app/fine/pdra.py:912-925 prints, plus the counts.  Minima and maxima run over the non-NaN elements ([n,3] values,
  * not per-ray maxima) of all rays, of the set (uncertain) rays and of the clear (certain) rays; an empty group holds +inf
@@ -1448,30 +1448,14 @@ typedef struct esr_regroup_stats_t {
 int esr_emit_decide(const float *emission, int64_t n, float k_val, uint8_t *flags, esr_regroup_stats_t *stats,
                     int accumulate, void *stream);
 /*
- * Counts for the partition below (two launches: a count per tile, then a one-block exclusive scan).  block_offsets i64
- * [ceil(n / ESR_PARTITION_BLOCK)]: the number of set (non-zero) flags in front of tile b; totals i64 [2] = (set, clear).
- * Replaces the counting inside the boolean indexings of utils2/utils.py:257-267.
- */
-int esr_flag_scan(const uint8_t *flags, int64_t n, int64_t *block_offsets, int64_t *totals, void *stream);
-/*
- * The stable two-way partition of RayGroupManager.filter (utils2/utils.py:264-267): set_out [totals[0]] = rows[flags != 0]
- * and clear_out [totals[1]] = rows[flags == 0], both in input order.  rows i64 [n] is not written; set_out and clear_out
- * must not alias it or each other; clear_out may point into the middle of a larger buffer (the certain group's new vector,
- * behind its old contents).  flags and block_offsets as esr_flag_scan left them.  An output of size 0 may be NULL: the
- * CALLER guarantees that a NULL output's side is empty (totals says so); the kernel cannot check it and skips the stores of
- * rows that would go to a NULL output, only two NULL outputs are ESR_EINVAL.
- */
-int esr_index_partition(const int64_t *rows, const uint8_t *flags, const int64_t *block_offsets, int64_t n,
-                        int64_t *set_out, int64_t *clear_out, void *stream);
-
-/*
- * The same flags as packed 64-bit words, for a re-split under data parallelism (esr_nerf_amd/csrc/regroup_dp.hip).  Packed
- * format: bit b of word w is the flag of ray 64 w + b, bit 0 the least significant; the bits at and above n in the last word
- * are 0; words u64 [ceil(n / 64)], 8-byte aligned.  Shares of a flag vector that are cut at word boundaries combine under an
- * integer SUM all-reduce of the words (zero outside a rank's share).
+ * The same flags as packed 64-bit words: what the scan and the partition below read, and what a re-split under data
+ * parallelism all-reduces.  Packed format: bit b of word w is the flag of ray 64 w + b, bit 0 the least significant; the
+ * bits at and above n in the last word are 0; words u64 [ceil(n / 64)], 8-byte aligned.  Shares of a flag vector that are cut
+ * at word boundaries combine under an integer SUM all-reduce of the words (zero outside a rank's share).
  *
  * esr_emit_decide_bits: the decision and the statistics of esr_emit_decide (the same comparison, NaN rule, counts, minima and
- * maxima, the same `accumulate`), written as ceil(n / 64) WHOLE words, one wave ballot each, instead of n bytes.
+ * maxima, the same `accumulate`), written as ceil(n / 64) WHOLE words, one wave ballot each, instead of n bytes: a chunk of a
+ * longer flag vector starts on a word (a multiple of 64 rays), where a chunk of esr_emit_decide may start at any ray.
  */
 int esr_emit_decide_bits(const float *emission, int64_t n, float k_val, uint64_t *words, esr_regroup_stats_t *stats,
                          int accumulate, void *stream);
@@ -1480,11 +1464,20 @@ int esr_flags_pack(const uint8_t *flags, int64_t n, uint64_t *words, void *strea
 /* words -> flags u8 [n]: exactly 0 or 1 per byte */
 int esr_flags_unpack(const uint64_t *words, int64_t n, uint8_t *flags, void *stream);
 /*
- * esr_flag_scan on packed words: block_offsets and totals mean what they mean there (a tile is ESR_PARTITION_BLOCK flags =
- * 16 words, counts are popcounts), so either form feeds either partition's offsets.
+ * Counts for the partition below (two launches: a count per tile, then a one-block exclusive scan).  block_offsets i64
+ * [ceil(n / ESR_PARTITION_BLOCK)]: the number of set flags in front of tile b (a tile is ESR_PARTITION_BLOCK flags = 16
+ * words, counts are popcounts); totals i64 [2] = (set, clear).  Replaces the counting inside the boolean indexings of
+ * utils2/utils.py:257-267.
  */
 int esr_flag_scan_bits(const uint64_t *words, int64_t n, int64_t *block_offsets, int64_t *totals, void *stream);
-/* esr_index_partition on packed words: the same stable two-way partition, the same rule for a NULL output. */
+/*
+ * The stable two-way partition of RayGroupManager.filter (utils2/utils.py:264-267): set_out [totals[0]] = the rows whose flag
+ * is set and clear_out [totals[1]] = the rows whose flag is clear, both in input order.  rows i64 [n] is not written; set_out
+ * and clear_out must not alias it or each other; clear_out may point into the middle of a larger buffer (the certain group's
+ * new vector, behind its old contents).  words and block_offsets as esr_flag_scan_bits left them.  An output of size 0 may be
+ * NULL: the CALLER guarantees that a NULL output's side is empty (totals says so); the kernel cannot check it and skips the
+ * stores of rows that would go to a NULL output, only two NULL outputs are ESR_EINVAL.
+ */
 int esr_index_partition_bits(const int64_t *rows, const uint64_t *words, const int64_t *block_offsets, int64_t n,
                              int64_t *set_out, int64_t *clear_out, void *stream);
 /*

@@ -1,5 +1,5 @@
 """Restatement in numpy of what the re-split under data parallelism adds to tests/regroup_ref.py (esr_nerf_amd/regroup.py
-over csrc/regroup_dp.hip): the packed flag words, the ranks' shares, the merge of the ranks' records -- and the worker that
+over csrc/regroup.hip): the packed flag words, the ranks' shares, the merge of the ranks' records -- and the worker that
 tests/test_regroup_dp_host.py (gloo ranks on the CPU) and tests/test_gpu_regroup_dp.py (gloo ranks on the one GPU) start under
 ``torch.distributed.run``."""
 import numpy as np
@@ -184,7 +184,19 @@ if "stub" in PARTS or "fail" in PARTS:
             up, dn = np.nextafter(k32, np.float32(np.inf)), np.nextafter(k32, np.float32(-np.inf))
             m = np.fmax.reduce(e_u, axis=1)
             assert (m == k32).any() and (m == up).any() and (m == dn).any() and np.isnan(e_u).any(), name
-        one = regroup.update_ray_groups(Stub(table), s1, k, batch_size=bs, verbose=False, return_emission=True)
+        u1, c1 = s1.uncert_data_idxs.clone(), s1.cert_data_idxs.clone()
+        stub1 = Stub(table)
+        one = regroup.update_ray_groups(stub1, s1, k, batch_size=bs, verbose=False, return_emission=True)
+        # the single-process run: chunks of exactly batch_size rays (they may start inside a word), the restatement's flags,
+        # and the groups that filter makes of them
+        size1 = regroup.DEFAULT_BATCH_SIZE if bs is None else bs
+        assert [len(r) for r in stub1.rows] == [min(size1, n_u - a) for a in range(0, n_u, size1)], (name, [len(r) for r in stub1.rows])
+        want1 = torch.from_numpy(R.decide(table[u0.to(DEVICE)].cpu().numpy(), np.float32(k)))
+        assert one.flags.dtype == torch.bool and torch.equal(one.flags.cpu(), want1), name
+        twin = RayGroupManager(AttrDict(system=dict(device="cpu", data_preload="cpu")), {k_: torch.zeros(n_u + n_c, 3) for k_ in KEYS},
+                               list(KEYS), 24, 8, 48, 16, u1.cpu(), c1.cpu())
+        twin.filter(want1)
+        assert torch.equal(s1.uncert_data_idxs.cpu(), twin.uncert_data_idxs) and torch.equal(s1.cert_data_idxs.cpu(), twin.cert_data_idxs), name
         stub = Stub(table)
         rep = regroup.update_ray_groups(stub, s, k, batch_size=bs, verbose=False, return_emission=True, process_group=WORLD)
         assert stub.mode() == "train" and set(stub.modes_seen) <= {"eval"}, name

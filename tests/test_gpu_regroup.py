@@ -1,6 +1,7 @@
-"""PDRA's ray re-split on the MI355X (esr_nerf_amd/regroup.py over csrc/regroup.hip): ``esr_emit_decide``, ``esr_flag_scan``
-and ``esr_index_partition`` through the C ABI against the numpy restatement tests/regroup_ref.py and torch's own indexing,
-exact, with guards and shifted pointers; ``update_ray_groups`` on the reference's recorded emission (tests/golden/
+"""PDRA's ray re-split on the MI355X (esr_nerf_amd/regroup.py over csrc/regroup.hip): ``esr_emit_decide``, and
+``esr_flags_pack`` -> ``esr_flag_scan_bits`` -> ``esr_index_partition_bits`` on packed words, through the C ABI against the
+numpy restatements tests/regroup_ref.py and tests/regroup_dp_ref.py and torch's own indexing, exact, with guards and shifted
+pointers; ``update_ray_groups`` on the reference's recorded emission (tests/golden/
 lts_g16_evals*.npz), on a progressive sequence against the CPU oracle outside its decision band, on a camera-defined set, and
 in front of a PDRA training step."""
 import ctypes as C
@@ -11,6 +12,7 @@ import pytest
 import torch
 
 import camera_ref as CR
+import regroup_dp_ref as D
 import regroup_ref as R
 from conftest import load_npz, rel_err
 
@@ -101,57 +103,98 @@ def test_decide_wrapper_merges_chunks_into_one_record():
     assert not R.same_stats(regroup.read_stats(empty), R.stats(np.zeros((0, 3), np.float32), np.zeros(0, bool)))
 
 
-# ---- esr_flag_scan, esr_index_partition ------------------------------------------------------------------------------------------
+# ---- esr_flags_pack, esr_flags_unpack, esr_flag_scan_bits, esr_index_partition_bits -----------------------------------------------
 def _partition_sizes():
     L = _lib()
     pb, st = L.PARTITION_BLOCK, L.PARTITION_SCAN_TILE
     assert (pb, st) == (1024, 1024)
-    return sorted(set(SIZES + [pb * k + d for k in (1, 2) for d in (-1, 0, 1)] + [(st + 1) * pb + 1]))
+    # around one and two tiles; a ragged last tile and a ragged last word; a second trip of the one-block scan, twice
+    return sorted(set(SIZES + [pb * k + d for k in (1, 2) for d in (-1, 0, 1)] + [4 * pb + 37, st * pb + 70000, (st + 1) * pb + 1]))
 
 
-PARTITION_SIZES = sorted(set(SIZES + [1023, 1024, 1025, 2047, 2048, 2049, 1025 * 1024 + 1]))
+PARTITION_SIZES = sorted(set(SIZES + [1023, 1024, 1025, 2047, 2048, 2049, 4096 + 37, 1024 * 1024 + 70000, 1025 * 1024 + 1]))
 GUARD = -0x0123456789ABCDEF
+
+
+def _patterns(n, seed):
+    p = R.flag_patterns(n, seed)
+    p["random_50"] = np.random.default_rng(seed + 1).random(n) < 0.5
+    return p
+
+
+def _guarded(n, fill=GUARD, dtype=torch.int64, shift=1):
+    """A buffer with G guard elements in front of and behind n elements that start `shift` elements further in (so an int64
+    output sits 8 bytes off the allocation's alignment) -> (buffer, byte offset of the output, check(name) -> the output)"""
+    buf = torch.full((n + 2 * G + shift,), fill, dtype=dtype, device=DEV)
+    lo = G + shift
+
+    def check(name):
+        assert bool((buf[:lo] == fill).all()) and bool((buf[lo + n:] == fill).all()), name
+        return buf[lo:lo + n]
+
+    return buf, lo * buf.element_size(), check
 
 
 @pytest.mark.parametrize("n", PARTITION_SIZES)
 def test_scan_and_partition_equal_boolean_indexing(n):
+    """pack -> scan -> partition on words against numpy and torch's boolean indexing"""
     L = _lib()
+    lib = L.lib()
     assert PARTITION_SIZES == _partition_sizes()
     pb = L.PARTITION_BLOCK
-    n_tiles = -(-n // pb)
+    nw, n_tiles = D.n_words(n), -(-n // pb)
+    assert n < 1024 * 1024 or n_tiles > L.PARTITION_SCAN_TILE         # the two largest: a second trip of the one-block scan
     rng = np.random.default_rng(n)
     rows_h = rng.integers(0, 1 << 62, size=n, dtype=np.int64)
     rows_h[::3] += 1 << 40
     assert n == 0 or rows_h.max() > 1 << 40
-    rows = torch.from_numpy(rows_h).to(DEV)
+    rows_buf = torch.zeros(n + 1, dtype=torch.int64, device=DEV)      # the rows start 8 bytes into their allocation
+    rows = rows_buf[1:]
+    rows.copy_(torch.from_numpy(rows_h))
     rows0 = rows.clone()
-    for name, f in R.flag_patterns(n, n + 1).items():
+    for name, f in _patterns(n, n + 1).items():
         fh = f.astype(np.uint8)
-        fh[f & (np.arange(n) % 5 == 0)] = 255                       # any non-zero byte is a set flag
-        flags = torch.from_numpy(fh).to(DEV)
+        fh[f & (np.arange(n) % 5 == 0)] = 255                        # any non-zero byte is a set flag
+        fbuf = torch.zeros(n + 1, dtype=torch.uint8, device=DEV)
+        flags = fbuf[1:]                                             # (bytes at an odd address)
+        flags.copy_(torch.from_numpy(fh))
         flags0 = flags.clone()
         n_set = int(f.sum())
-        off = torch.full((n_tiles + 2 * G,), GUARD, dtype=torch.int64, device=DEV)
-        tot = torch.full((2 + 2 * G,), GUARD, dtype=torch.int64, device=DEV)
-        set_out = torch.full((n_set + 2 * G,), GUARD, dtype=torch.int64, device=DEV)
-        clear_buf = torch.full((3 + n - n_set + G,), GUARD, dtype=torch.int64, device=DEV)
-        assert L.lib().esr_flag_scan(_p(flags), n, _p(off, 8 * G), _p(tot, 8 * G), _stream()) == 0
-        assert L.lib().esr_index_partition(_p(rows), _p(flags), _p(off, 8 * G), n, _p(set_out, 8 * G), _p(clear_buf, 24),
-                                           _stream()) == 0
+        want_words = D.pack(f)
+        wbuf, woff, wcheck = _guarded(nw)
+        ubuf, uoff, ucheck = _guarded(n, 0xA5, torch.uint8)
+        obuf, ooff, ocheck = _guarded(n_tiles)
+        tbuf, toff, tcheck = _guarded(2)
+        sbuf, soff, scheck = _guarded(n_set)
+        clear_buf = torch.full((3 + n - n_set + G,), GUARD, dtype=torch.int64, device=DEV)     # clear_out in its middle
+        assert lib.esr_flags_pack(_p(flags), n, _p(wbuf, woff), _stream()) == 0
+        assert lib.esr_flags_unpack(_p(wbuf, woff), n, _p(ubuf, uoff), _stream()) == 0
+        assert lib.esr_flag_scan_bits(_p(wbuf, woff), n, _p(obuf, ooff), _p(tbuf, toff), _stream()) == 0
+        assert lib.esr_index_partition_bits(_p(rows), _p(wbuf, woff), _p(obuf, ooff), n, _p(sbuf, soff), _p(clear_buf, 24),
+                                            _stream()) == 0
         torch.cuda.synchronize()
         assert torch.equal(rows, rows0) and torch.equal(flags, flags0), name
-        if n == 0:
-            assert all(bool((t == GUARD).all()) for t in (off, tot, set_out, clear_buf)), name
+        if n == 0:                                                   # n == 0 touches nothing
+            assert all(bool((t == GUARD).all()) for t in (wbuf, obuf, tbuf, sbuf, clear_buf)) and bool((ubuf == 0xA5).all()), name
             continue
-        fd = flags != 0
+        # pack: whole words, the tail of the last one clear, guards untouched (also after the scan and the partition read them)
+        words = wcheck(name)
+        assert np.array_equal(words.cpu().numpy().view(np.uint64), want_words), name
+        if n % 64:
+            assert int(want_words[-1]) >> (n % 64) == 0 and int(words[-1].cpu().numpy().view(np.uint64)) >> (n % 64) == 0, name
+        # unpack: exactly 0 or 1, the round trip
+        assert np.array_equal(ucheck(name).cpu().numpy(), f.astype(np.uint8)), name
+        # scan on words == numpy
         per_tile = np.add.reduceat(f.astype(np.int64), np.arange(0, n, pb))
         want_off = np.concatenate([[0], np.cumsum(per_tile)[:-1]])
-        assert np.array_equal(off[G:G + n_tiles].cpu().numpy(), want_off), name
-        assert tot[G:G + 2].tolist() == [n_set, n - n_set], name
-        assert torch.equal(set_out[G:G + n_set], rows[fd]), name
+        assert np.array_equal(ocheck(name).cpu().numpy(), want_off), name
+        assert tcheck(name).tolist() == [n_set, n - n_set], name
+        # partition on words == boolean indexing
+        fd = flags != 0
+        assert torch.equal(fd, torch.from_numpy(f).to(DEV)), name
+        assert torch.equal(scheck(name), rows[fd]), name
         assert torch.equal(clear_buf[3:3 + n - n_set], rows[~fd]), name
-        for t, lo, hi in ((off, G, G + n_tiles), (tot, G, G + 2), (set_out, G, G + n_set), (clear_buf, 3, 3 + n - n_set)):
-            assert bool((t[:lo] == GUARD).all()) and bool((t[hi:] == GUARD).all()), name
+        assert bool((clear_buf[:3] == GUARD).all()) and bool((clear_buf[3 + n - n_set:] == GUARD).all()), name
 
 
 def test_partition_wrapper_and_apply_flags_on_a_device_sampler():
@@ -173,6 +216,18 @@ def test_partition_wrapper_and_apply_flags_on_a_device_sampler():
         assert (b.uncert_batch_st, b.cert_batch_st) == (48, 16)
         s, c = regroup.partition(perm[:n_u].to(DEV), flags)
         assert torch.equal(s, a.uncert_data_idxs) and torch.equal(c, a.cert_data_idxs[n_c:]), name
+    # uint8 flags: any non-zero byte is a set flag
+    f8 = torch.from_numpy((np.random.default_rng(7).random(n_u) < 0.5).astype(np.uint8))
+    f8[(f8 != 0) & (torch.arange(n_u) % 3 == 0)] = 2
+    f8[(f8 != 0) & (torch.arange(n_u) % 3 == 1)] = 255
+    assert {0, 1, 2, 255} == set(f8.unique().tolist())
+    rows, flags = perm[:n_u].to(DEV), f8.to(DEV)
+    s, c = regroup.partition(rows, flags)
+    assert torch.equal(s, rows[flags != 0]) and torch.equal(c, rows[flags == 0])
+    b = RayGroupManager(cfg, data, list(data), 24, 8, 48, 16, perm[:n_u], perm[n_u:])
+    old_c = b.cert_data_idxs.clone()
+    assert regroup.apply_flags(b, flags) is None
+    assert torch.equal(b.uncert_data_idxs, rows[flags != 0]) and torch.equal(b.cert_data_idxs, torch.cat([old_c, rows[flags == 0]]))
 
 
 # ---- update_ray_groups -----------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
-"""PDRA's re-split under data parallelism on the MI355X (esr_nerf_amd/regroup.py over csrc/regroup_dp.hip): the packed-word
-entry points through the C ABI, exactly, against the numpy restatement tests/regroup_dp_ref.py and against the byte kernels of
-csrc/regroup.hip on the same flags, with guards and shifted pointers; the wrappers on a device sampler; and
+"""PDRA's re-split under data parallelism on the MI355X (esr_nerf_amd/regroup.py over csrc/regroup.hip): the decision into
+words and the merge of the ranks' records through the C ABI, exactly, against the numpy restatement tests/regroup_dp_ref.py
+and the byte decision on the same emission, with guards and shifted pointers (pack, scan and partition on words:
+tests/test_gpu_regroup.py); the wrappers on a device sampler; and
 ``update_ray_groups(..., process_group=)`` with two and three ranks on the one GPU over gloo (the worker of
 tests/regroup_dp_ref.py) against the single-process byte path, with a stub renderer, the real g16 model, a camera-defined
 set, and a data-parallel PDRA step after the re-split."""
@@ -54,67 +55,6 @@ def _guarded(n, fill=GUARD, dtype=torch.int64, shift=1):
         return buf[lo:lo + n]
 
     return buf, lo * buf.element_size(), check
-
-
-@pytest.mark.parametrize("n", SIZES)
-def test_pack_scan_and_partition_on_words_equal_the_restatement_and_the_byte_kernels(n):
-    L = _lib()
-    lib = L.lib()
-    nw, n_tiles = D.n_words(n), -(-n // L.PARTITION_BLOCK)
-    assert L.PARTITION_BLOCK == 1024 and (n < SIZES[-1] or n_tiles > L.PARTITION_SCAN_TILE)
-    rng = np.random.default_rng(n)
-    rows_h = rng.integers(0, 1 << 62, size=n, dtype=np.int64)
-    rows_buf = torch.zeros(n + 1, dtype=torch.int64, device=DEV)      # the rows start 8 bytes into their allocation
-    rows = rows_buf[1:]
-    rows.copy_(torch.from_numpy(rows_h))
-    rows0 = rows.clone()
-    for name, f in _patterns(n, n + 1).items():
-        fh = f.astype(np.uint8)
-        fh[f & (np.arange(n) % 5 == 0)] = 255                        # any non-zero byte is a set flag
-        fbuf = torch.zeros(n + 1, dtype=torch.uint8, device=DEV)
-        flags = fbuf[1:]                                             # (bytes at an odd address)
-        flags.copy_(torch.from_numpy(fh))
-        flags0 = flags.clone()
-        n_set = int(f.sum())
-        want_words = D.pack(f)
-        # pack: whole words, the tail of the last one clear, guards untouched
-        wbuf, woff, wcheck = _guarded(nw)
-        assert lib.esr_flags_pack(_p(flags), n, _p(wbuf, woff), _stream()) == 0
-        words = wcheck(name)
-        assert np.array_equal(words.cpu().numpy().view(np.uint64), want_words), name
-        if n % 64:
-            assert int(want_words[-1]) >> (n % 64) == 0 and int(words[-1].cpu().numpy().view(np.uint64)) >> (n % 64) == 0, name
-        # unpack: exactly 0 or 1, the round trip
-        ubuf, uoff, ucheck = _guarded(n, 0xA5, torch.uint8)
-        assert lib.esr_flags_unpack(_p(wbuf, woff), n, _p(ubuf, uoff), _stream()) == 0
-        assert np.array_equal(ucheck(name).cpu().numpy(), f.astype(np.uint8)), name
-        # scan on words == numpy == the byte scan
-        obuf, ooff, ocheck = _guarded(n_tiles)
-        tbuf, toff, tcheck = _guarded(2)
-        assert lib.esr_flag_scan_bits(_p(wbuf, woff), n, _p(obuf, ooff), _p(tbuf, toff), _stream()) == 0
-        off_b, tot_b = torch.empty(n_tiles, dtype=torch.int64, device=DEV), torch.empty(2, dtype=torch.int64, device=DEV)
-        assert lib.esr_flag_scan(_p(flags), n, _p(off_b), _p(tot_b), _stream()) == 0
-        per_tile = np.add.reduceat(f.astype(np.int64), np.arange(0, n, L.PARTITION_BLOCK))
-        want_off = np.concatenate([[0], np.cumsum(per_tile)[:-1]])
-        off = ocheck(name)
-        assert np.array_equal(off.cpu().numpy(), want_off) and torch.equal(off, off_b), name
-        assert tcheck(name).tolist() == [n_set, n - n_set] == tot_b.tolist(), name
-        # partition on words == boolean indexing == the byte partition; clear_out in the middle of a larger buffer
-        sbuf, soff, scheck = _guarded(n_set)
-        clear_buf = torch.full((3 + n - n_set + G,), GUARD, dtype=torch.int64, device=DEV)
-        assert lib.esr_index_partition_bits(_p(rows), _p(wbuf, woff), _p(obuf, ooff), n, _p(sbuf, soff), _p(clear_buf, 24),
-                                            _stream()) == 0
-        set_b, clear_b = torch.empty(n_set, dtype=torch.int64, device=DEV), torch.empty(n - n_set, dtype=torch.int64, device=DEV)
-        assert lib.esr_index_partition(_p(rows), _p(flags), _p(off_b), n, _p(set_b) if n_set else None,
-                                       _p(clear_b) if n - n_set else None, _stream()) == 0
-        torch.cuda.synchronize()
-        fd = torch.from_numpy(f).to(DEV)
-        assert torch.equal(rows, rows0) and torch.equal(flags, flags0) and np.array_equal(wcheck(name).cpu().numpy().view(np.uint64), want_words), name
-        got_set, got_clear = scheck(name), clear_buf[3:3 + n - n_set]
-        assert torch.equal(got_set, rows[fd]) and torch.equal(got_set, set_b), name
-        assert torch.equal(got_clear, rows[~fd]) and torch.equal(got_clear, clear_b), name
-        assert bool((clear_buf[:3] == GUARD).all()) and bool((clear_buf[3 + n - n_set:] == GUARD).all()), name
-        ocheck(name), tcheck(name)
 
 
 def _rec_bytes(r):

@@ -1,4 +1,4 @@
-"""CPU side of PDRA's re-split under data parallelism (esr_nerf_amd/regroup.py over csrc/regroup_dp.hip): the ranks' shares,
+"""CPU side of PDRA's re-split under data parallelism (esr_nerf_amd/regroup.py over csrc/regroup.hip): the ranks' shares,
 the packed flag words against numpy, ``apply_flags`` on words, ``update_ray_groups(..., process_group=)`` with two and three real
 gloo ranks and a stub renderer against the single-process run (tests/regroup_dp_ref.py: WORKER), and the C ABI's declarations."""
 import ctypes

@@ -17,7 +17,7 @@ from esr_nerf_amd.config import AttrDict
 from esr_nerf_amd.data import RayGroupManager
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENTRIES = ("esr_emit_decide", "esr_flag_scan", "esr_index_partition")
+ENTRIES = ("esr_emit_decide",)
 K = 0.40575385
 KEYS = ["rays_o", "rays_d", "viewdirs"]
 
@@ -290,5 +290,3 @@ def test_entry_points_check_their_arguments_before_any_launch():
     for n, code in ((0, 0), (-1, -1), (1 << 31, -2), ((1 << 31) + 5, -2), (5, -1)):
         assert L.esr_emit_decide(null, n, 0.5, null, null, 0, null) == code, n
         assert L.esr_emit_decide(null, n, 0.5, null, null, 1, null) == code, n
-        assert L.esr_flag_scan(null, n, null, null, null) == code, n
-        assert L.esr_index_partition(null, null, null, n, null, null, null) == code, n

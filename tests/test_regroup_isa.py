@@ -1,6 +1,7 @@
 """Checks on the generated gfx950 code of csrc/regroup.hip (compiled with the product's flags through esr_nerf_amd/build.py,
-as tests/test_relight_isa.py does; CPU only).  Every kernel keeps everything in registers: no scratch memory, no spills, and
-few enough vector registers for the eight waves per SIMD the design note claims (at most 64 registers per lane)."""
+as tests/test_relight_isa.py does; CPU only).  The file holds exactly the kernels listed here, and every one keeps everything
+in registers: no scratch memory, no spills, and few enough vector registers for the eight waves per SIMD the design note
+claims (at most 64 registers per lane).  Registers and scratch are all this test looks at."""
 import os
 import sys
 
@@ -9,7 +10,8 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import kernel_meta as km      # noqa: E402
 
 EIGHT_WAVES = 64              # allocated vector + accumulation registers per lane that still admit 8 waves per SIMD
-KERNELS = ("regroup_stats_init_kernel", "emit_decide_kernel", "flag_count_kernel", "flag_scan_kernel", "index_partition_kernel")
+KERNELS = ("regroup_stats_init_kernel", "emit_decide_kernel", "emit_decide_bits_kernel", "flags_pack_kernel", "flags_unpack_kernel",
+           "flag_count_bits_kernel", "flag_scan_kernel", "index_partition_bits_kernel", "regroup_stats_merge_kernel")
 
 
 def test_regroup_kernels_use_no_scratch_and_fit_eight_waves():

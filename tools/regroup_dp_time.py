@@ -1,14 +1,15 @@
-"""Times of PDRA's re-split with packed flag words (esr_nerf_amd/csrc/regroup_dp.hip) against the byte kernels
-(csrc/regroup.hip), and a two-rank flow rehearsal of ``update_ray_groups(..., process_group=)``.
+"""Times of PDRA's re-split on packed flag words as a rank under data parallelism runs it (esr_nerf_amd/csrc/regroup.hip), and a
+two-rank flow rehearsal of ``update_ray_groups(..., process_group=)``.
 
-    python tools/regroup_dp_time.py [--rows 67108864] [--repeats 10] [--rounds 3] [--out profiles/regroup_dp_time.json]
+    python tools/regroup_dp_time.py [--rows 67108864] [--repeats 10] [--rounds 3] [--out FILE]
 
 (a) ``--rows`` rows (2^26: 100 views of 800 x 800 are 64 M rays) at three set shares (1 %, 50 %, 99 %: emission uniform in
-    [0, 1), ``k_val = (1 - share)^(1/3)``): decide + scan + partition with one byte per flag against one bit per flag, in the
-    same process, and scan + partition alone.  Device events around each form, one warm-up, ``--repeats`` runs per round and
-    their median, ``--rounds`` rounds alternating the two forms; ``ms`` is the median of the rounds' medians, ``spread`` the
-    range of the rounds' medians over it.  The outputs of the two forms are compared for equality first.
-    ``packed_scan_partition_slower_beyond_spread`` says whether the packed form lost by more than the larger spread.
+    [0, 1), ``k_val = (1 - share)^(1/3)``): ``esr_emit_decide_bits`` + ``esr_flag_scan_bits`` + ``esr_index_partition_bits``, and
+    scan + partition alone.  Device events around each form, one warm-up, ``--repeats`` runs per round and their median,
+    ``--rounds`` rounds alternating the forms; ``ms`` is the median of the rounds' medians, ``spread`` the range of the rounds'
+    medians over it.  The outputs are compared with torch's boolean indexing first.  (profiles/regroup_dp_time.json is the
+    record of this tool at ABI 38, when it timed the byte scan and partition beside the packed ones: the comparison that
+    removed them.  tools/regroup_time.py times the single-process form, decide into bytes + pack + scan + partition.)
 (b) FLOW REHEARSAL, not a scaling measurement: a re-split of the g16 slab model's rays by two ranks that SHARE the one GPU
     over gloo (as ``ESR_BENCH_REHEARSAL`` does for bench.py; RCCL refuses two ranks per device) against the single-process
     re-split in the same setting.  It shows that the flow runs and what its fixed costs are on one card; both ranks compete
@@ -55,53 +56,33 @@ def kernels_at(n, share, repeats, rounds):
     k_val = float((1.0 - share) ** (1.0 / 3.0))
     rows = torch.randperm(n, device=dev, generator=g)
     n_tiles = (n + _lib.PARTITION_BLOCK - 1) // _lib.PARTITION_BLOCK
-    new = lambda m, dt=torch.int64: torch.empty(m, dtype=dt, device=dev)
-    flags, words = new(n, torch.uint8), new((n + 63) // 64)
-    st, off, tot = new(6), new(n_tiles), new(2)
-    out = {form: (new(n), new(n)) for form in ("bytes", "packed")}
+    new = lambda m: torch.empty(m, dtype=torch.int64, device=dev)
+    words, st, off, tot, so, co = new((n + 63) // 64), new(6), new(n_tiles), new(2), new(n), new(n)
 
     def check(code):
         if code:
             raise RuntimeError(f"entry point failed with code {code}")
 
-    def decide(form):
-        if form == "bytes":
-            check(L.esr_emit_decide(p(e), n, k_val, p(flags), p(st), 0, sp))
-        else:
-            check(L.esr_emit_decide_bits(p(e), n, k_val, p(words), p(st), 0, sp))
+    def decide():
+        check(L.esr_emit_decide_bits(p(e), n, k_val, p(words), p(st), 0, sp))
 
-    def scan_partition(form):
-        so, co = out[form]
-        if form == "bytes":
-            check(L.esr_flag_scan(p(flags), n, p(off), p(tot), sp))
-            check(L.esr_index_partition(p(rows), p(flags), p(off), n, p(so), p(co), sp))
-        else:
-            check(L.esr_flag_scan_bits(p(words), n, p(off), p(tot), sp))
-            check(L.esr_index_partition_bits(p(rows), p(words), p(off), n, p(so), p(co), sp))
+    def scan_partition():
+        check(L.esr_flag_scan_bits(p(words), n, p(off), p(tot), sp))
+        check(L.esr_index_partition_bits(p(rows), p(words), p(off), n, p(so), p(co), sp))
 
-    variants = {}
-    for form in ("bytes", "packed"):
-        variants[f"{form}_decide_scan_partition"] = lambda form=form: (decide(form), scan_partition(form))
-        variants[f"{form}_scan_partition"] = lambda form=form: scan_partition(form)
-    totals = {}
-    for form in ("bytes", "packed"):                         # warm-up, and the two forms' outputs
-        decide(form)
-        scan_partition(form)
-        totals[form] = tot.tolist()
-    n_set = totals["bytes"][0]
-    equal = totals["bytes"] == totals["packed"] and all(
-        bool(torch.equal(out["bytes"][i][:m], out["packed"][i][:m])) for i, m in ((0, n_set), (1, n - n_set)))
+    variants = {"packed_decide_scan_partition": lambda: (decide(), scan_partition()), "packed_scan_partition": scan_partition}
+    decide()                                                 # warm-up, and the outputs against torch
+    scan_partition()
+    n_set = int(tot[0])
+    keep = e.max(1)[0] > k_val
+    equal = bool(torch.equal(so[:n_set], rows[keep]) and torch.equal(co[:n - n_set], rows[~keep]))
+    del keep
     times = {k: [] for k in variants}
     for _ in range(rounds):
         for name, fn in variants.items():
             times[name].append([run_ms(fn) for _ in range(repeats)])
     res = {k: summary(v) for k, v in times.items()}
-    b, q = res["bytes_scan_partition"], res["packed_scan_partition"]
-    res.update(k_val=k_val, set_share=round(n_set / n, 5), outputs_equal=equal,
-               packed_over_bytes_scan_partition=round(q["ms"] / b["ms"], 4),
-               packed_over_bytes_decide_scan_partition=round(res["packed_decide_scan_partition"]["ms"] /
-                                                             res["bytes_decide_scan_partition"]["ms"], 4),
-               packed_scan_partition_slower_beyond_spread=bool(q["ms"] > b["ms"] * (1 + max(b["spread"], q["spread"]))))
+    res.update(k_val=k_val, set_share=round(n_set / n, 5), outputs_equal_torch=equal)
     return res
 
 

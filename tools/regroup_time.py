@@ -1,6 +1,7 @@
 """Times of PDRA's ray re-split (esr_nerf_amd/regroup.py) on the device.
 
-    python tools/regroup_time.py [--rays 1048576] [--rows 64000000] [--repeats 5] [--rounds 3] [--out profiles/regroup_time.json]
+    python tools/regroup_time.py [--rays 1048576] [--rows 64000000] [--share-rows 67108864] [--repeats 5] [--rounds 3]
+                                 [--kernels-only] [--out profiles/regroup_time.json]
 
 The case of tools/relight_time.py: the C2 slab scene with ``--rays`` rays, all uncertain, the index vectors on the device;
 ``k_val`` is the median of the per-ray maxima, so about half of the rays move.  Device events around whole calls (host time
@@ -10,10 +11,14 @@ rounds interleaving every variant; the spread reported is that of the rounds' me
       evaluate them) over this package's ``eval_emit`` and ``RayGroupManager.filter`` at chunk 4096
   (b) ``update_ray_groups`` (verbose, so the statistics are read) at chunks 4096, 16384, 65536 and 262144, with the peak
       device memory of a call and what stays allocated after it (the engine keeps the buffers of its largest chunk)
-  (c) ``apply_flags`` (flag scan + read-back + allocation + copy of the old certain vector + partition) against
-      ``RayGroupManager.filter`` (two boolean indexings + cat) on ``--rows`` int64 rows, and the two entry points alone
-Per-ray times are also scaled to 64 M rays (100 views of 800 x 800).  The default chunk is the smallest measured size whose
-time is within 5 % of the best.  One JSON line.
+  (c) ``apply_flags`` on byte flags (pack + flag scan + read-back + allocation + copy of the old certain vector + partition)
+      against ``RayGroupManager.filter`` (two boolean indexings + cat) on ``--rows`` int64 rows, and the three entry points
+      ``esr_flags_pack``, ``esr_flag_scan_bits`` and ``esr_index_partition_bits`` alone
+  (d) the device work of a single-process re-split behind ``eval_emit``: ``esr_emit_decide`` + ``esr_flags_pack`` +
+      ``esr_flag_scan_bits`` + ``esr_index_partition_bits`` on ``--share-rows`` rows (2^26) at set shares 1 %, 50 % and 99 %
+      (emission uniform in [0, 1), ``k_val = (1 - share)^(1/3)``), ``2 * --repeats`` runs per round
+``--kernels-only`` runs (c) and (d) alone.  Per-ray times are also scaled to 64 M rays (100 views of 800 x 800).  The default
+chunk is the smallest measured size whose time is within 5 % of the best.  One JSON line.
 """
 import argparse
 import contextlib
@@ -30,6 +35,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 CHUNKS = (4096, 16384, 65536, 262144)
+SHARES = (0.01, 0.5, 0.99)
 USER_RAYS = 64_000_000
 
 
@@ -71,18 +77,9 @@ def summary(per_round, n_rays):
                 ns_per_ray=round(m * 1e6 / n_rays, 4), ms_at_64M_rays=round(m * USER_RAYS / n_rays, 1))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--rays", type=int, default=1 << 20)
-    ap.add_argument("--rows", type=int, default=USER_RAYS)
-    ap.add_argument("--old-certain", type=int, default=4_000_000)
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--out", default=None)
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        sys.exit("regroup_time.py measures on the GPU; none is visible")
-    from esr_nerf_amd import _lib, regroup
+def loop_section(a):
+    """(a) and (b)"""
+    from esr_nerf_amd import regroup
     from esr_nerf_amd.config import lts_cfg
     from esr_nerf_amd.data import RayGroupManager
     from esr_nerf_amd.esrnerf import ESRNeRF
@@ -149,10 +146,13 @@ def main():
     default = next(c for c in CHUNKS if loop[f"update_ray_groups_{c}"]["ms"] <= 1.05 * best)
     base_ms = loop["retained_loop_4096"]["ms"]
     ratios = {str(c): round(base_ms / loop[f"update_ray_groups_{c}"]["ms"], 3) for c in CHUNKS}
-    del s, base, flags_of, ref_flags
-    torch.cuda.empty_cache()
+    return dict(scene="C2 slab", rays=n, k_val=k_val, loop=loop, speedup_over_retained_loop=ratios, default_batch_size=default)
 
-    # (c) the partition alone on --rows rows
+
+def partition_section(a):
+    """(c) the partition alone on --rows rows"""
+    from esr_nerf_amd import _lib, regroup
+    dev = torch.device("cuda:0")
     N = a.rows
     g = torch.Generator(device=dev).manual_seed(1)
     rows = torch.randperm(N, device=dev, generator=g)
@@ -170,14 +170,16 @@ def main():
         theirs.uncert_data_idxs = theirs.uncert_data_idxs[flags].contiguous()
 
     f8 = flags.view(torch.uint8)
+    words = torch.empty(regroup.n_words(N), dtype=torch.int64, device=dev)
     off = torch.empty((N + _lib.PARTITION_BLOCK - 1) // _lib.PARTITION_BLOCK, dtype=torch.int64, device=dev)
     tot = torch.empty(2, dtype=torch.int64, device=dev)
     so, co = torch.empty(N, dtype=torch.int64, device=dev), torch.empty(N, dtype=torch.int64, device=dev)
     L, sp = _lib.lib(), _lib.stream_ptr(dev)
     part = {"apply_flags": ours_fn, "torch_filter_lines": torch_fn,
-            "esr_flag_scan": lambda: L.esr_flag_scan(_lib.ptr(f8), N, _lib.ptr(off), _lib.ptr(tot), sp),
-            "esr_index_partition": lambda: L.esr_index_partition(_lib.ptr(rows), _lib.ptr(f8), _lib.ptr(off), N, _lib.ptr(so),
-                                                                 _lib.ptr(co), sp)}
+            "esr_flags_pack": lambda: L.esr_flags_pack(_lib.ptr(f8), N, _lib.ptr(words), sp),
+            "esr_flag_scan_bits": lambda: L.esr_flag_scan_bits(_lib.ptr(words), N, _lib.ptr(off), _lib.ptr(tot), sp),
+            "esr_index_partition_bits": lambda: L.esr_index_partition_bits(_lib.ptr(rows), _lib.ptr(words), _lib.ptr(off), N,
+                                                                           _lib.ptr(so), _lib.ptr(co), sp)}
     ptimes = {k: [] for k in part}
     for fn in part.values():
         fn()
@@ -187,14 +189,65 @@ def main():
         for name, fn in part.items():
             ptimes[name].append([run_ms(fn) for _ in range(2 * a.repeats)])
     partition = {k: summary(v, N) for k, v in ptimes.items()}
-    moved = N * (1 + 8 + 8)
-    partition["esr_index_partition"]["tb_per_s"] = round(moved / (partition["esr_index_partition"]["ms"] * 1e-3) / 1e12, 3)
+    moved = N * (8 + 8) + N // 8
+    partition["esr_index_partition_bits"]["tb_per_s"] = round(moved / (partition["esr_index_partition_bits"]["ms"] * 1e-3) / 1e12, 3)
     partition["speedup_apply_flags_over_torch"] = round(partition["torch_filter_lines"]["ms"] / partition["apply_flags"]["ms"], 3)
+    return dict(partition_rows=N, old_certain_rows=a.old_certain, partition=partition, partition_equals_torch=equal)
 
-    out = dict(scene="C2 slab", rays=n, k_val=k_val, repeats=a.repeats, rounds=a.rounds, loop=loop,
-               speedup_over_retained_loop=ratios, default_batch_size=default, module_default=regroup.DEFAULT_BATCH_SIZE,
-               partition_rows=N, old_certain_rows=a.old_certain, partition=partition, partition_equals_torch=equal,
-               device=torch.cuda.get_device_name(0))
+
+def resplit_kernels_at(n, share, repeats, rounds):
+    """(d) decide into bytes + pack + scan + partition on n rows at one set share"""
+    from esr_nerf_amd import _lib
+    dev = torch.device("cuda:0")
+    L, sp, p = _lib.lib(), _lib.stream_ptr(dev), _lib.ptr
+    g = torch.Generator(device=dev).manual_seed(int(share * 100))
+    e = torch.rand(n, 3, device=dev, generator=g)
+    k_val = float((1.0 - share) ** (1.0 / 3.0))
+    rows = torch.randperm(n, device=dev, generator=g)
+    new = lambda m, dt=torch.int64: torch.empty(m, dtype=dt, device=dev)
+    flags, words = new(n, torch.uint8), new((n + 63) // 64)
+    st, off, tot = new(6), new((n + _lib.PARTITION_BLOCK - 1) // _lib.PARTITION_BLOCK), new(2)
+    so, co = new(n), new(n)
+
+    def run():
+        codes = (L.esr_emit_decide(p(e), n, k_val, p(flags), p(st), 0, sp), L.esr_flags_pack(p(flags), n, p(words), sp),
+                 L.esr_flag_scan_bits(p(words), n, p(off), p(tot), sp),
+                 L.esr_index_partition_bits(p(rows), p(words), p(off), n, p(so), p(co), sp))
+        if any(codes):
+            raise RuntimeError(f"entry points failed with codes {codes}")
+
+    run()                                                    # warm-up, and the outputs against torch
+    n_set = int(tot[0])
+    keep = e.max(1)[0] > k_val
+    equal = bool(torch.equal(so[:n_set], rows[keep]) and torch.equal(co[:n - n_set], rows[~keep]))
+    del keep
+    res = summary([[run_ms(run) for _ in range(repeats)] for _ in range(rounds)], n)
+    res.update(k_val=k_val, set_share=round(n_set / n, 5), outputs_equal_torch=equal)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rays", type=int, default=1 << 20)
+    ap.add_argument("--rows", type=int, default=USER_RAYS)
+    ap.add_argument("--share-rows", type=int, default=1 << 26)
+    ap.add_argument("--old-certain", type=int, default=4_000_000)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--kernels-only", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("regroup_time.py measures on the GPU; none is visible")
+    from esr_nerf_amd import regroup
+    out = dict(repeats=a.repeats, rounds=a.rounds, module_default=regroup.DEFAULT_BATCH_SIZE, device=torch.cuda.get_device_name(0))
+    if not a.kernels_only:
+        out.update(loop_section(a))
+        torch.cuda.empty_cache()
+    out.update(partition_section(a))
+    torch.cuda.empty_cache()
+    out["resplit_kernels_rows"] = a.share_rows
+    out["resplit_kernels"] = {str(sh): resplit_kernels_at(a.share_rows, sh, 2 * a.repeats, a.rounds) for sh in SHARES}
     line = json.dumps(out)
     print(line, flush=True)
     if a.out:
