@@ -547,8 +547,28 @@ int esr_tone_wgrad_recompute_split(const float *Xt, const float *dzt, const floa
  * the esr_mlp_pack buffer.  The tiles saved for the backward -- H[l] and dZ[l] -- are bf16, hid * 32 values per tile
  * (half the bytes of the fp32 engine's) in an engine-private order: [row / 4][32 sample slots][4 rows], sample s in
  * slot 8 ((s >> 1) & 3) + 2 (s >> 3) + (s & 1) -- written 8 bytes per lane, read back only by esr_mlp_wgrad_bf16;
- * X, zout, dz, dX, the masks M and the weight / bias gradients are fp32 with the layouts above, so the
+ * X, zout, dz, dX and the weight / bias gradients are fp32 with the layouts above, so the
  * feature / shading kernels are shared.  packed16: esr_mlp_packed_bf16_elems(kind) bf16 values.
+ *
+ * What is rounded, and where (round to nearest, ties to even; tests/mlp_bf16_ref64.py restates exactly this):
+ *   forward          X on load (an X16 tile is that rounding, done by its writer), W by esr_mlp_pack_bf16; pre[l] = W16 h16 + b with
+ *                    exact products, fp32 sums and the fp32 bias; h[l] = relu(pre[l]) is rounded ONCE, and that bf16 value is the
+ *                    next layer's operand, the saved H[l] and the source of the mask bit (bit = stored H > 0 = pre > 0: a normal
+ *                    fp32 does not round to zero).  zout is the fp32 sum, not rounded.
+ *   input gradients  dz on load, W^T as packed; dZ[l] = mask (.) (fp32 sum) is rounded once: the stored tile and the next
+ *                    operand.  dX is the fp32 sum.  These kernels write the WHOLE [64][32] tile of dX: rows 0-63 with a
+ *                    reference column carry the gradient (the position / view encodings of rows 43-63 included), rows without
+ *                    one are exactly 0 -- unlike esr_mlp_dgrad, which leaves the rows above its documented count untouched.
+ *   weight gradients X and dz are rounded on staging, H / dZ / X16 tiles are used as stored; products exact, fp32 sums.
+ *                    gb[last] sums the UNROUNDED dz, a hidden layer's gb the stored bf16 dZ.
+ *   tone recompute   esr_tone_wgrad_recompute_bf16 rounds Xt (all 33 rows), W0, dzt and W1 for Ht = relu(W0 Xt + b0) and
+ *                    dZt = mask (.) (W1^T dzt), both fp32 sums; dW0's columns 0-31 take r(dZt) and r(Xt) on the matrix cores;
+ *                    dW0's column 32 (the 33rd input), db0, dW1 (= dzt Ht^T) and db1 are fp32 sums of the UNROUNDED
+ *                    dZt, Xt row 32, dzt and Ht on the vector lanes.
+ * The masks M are the [tile][word][lane] u32 arrays of esr_mlp_fwd with the same lane halves, but the bits of a word are in
+ * this engine's own order: feature 32 it + acc_row(r, h) of sample s is bit 8 (it & 1) + (r >> 1) + 16 (r & 1) of word it / 2
+ * in lane s + 32 h (the forward builds the word from packed bf16 pairs).  Masks written by esr_mlp_fwd_bf16 /
+ * esr_mlp_fwd_fine_bf16 are therefore read by esr_mlp_dgrad_bf16 / esr_mlp_dgrad_fine_bf16 only, and vice versa.
  */
 int64_t esr_mlp_packed_bf16_elems(int kind);
 int esr_mlp_pack_bf16(int kind, const esr_mlp_weights_t *w, void *packed16, void *stream);
