@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libesr_hip.so")
 # developer experiments only (python -m esr_nerf_amd.build --variant builds alternative libraries; tools/ab_env.sh times them
 # side by side on one box)
 LIB_PATH = os.environ.get("ESR_LIB_PATH", LIB_PATH)
-ABI_VERSION = 39
+ABI_VERSION = 40
 _lib = None
 
 
@@ -196,6 +196,7 @@ EXPORTS = [
     "esr_cc_link", "esr_cc_flatten", "esr_cc_face_labels", "esr_cc_stats",
     "esr_emit_decide", "esr_emit_decide_bits", "esr_flags_pack", "esr_flags_unpack", "esr_flag_scan_bits",
     "esr_index_partition_bits", "esr_regroup_stats_merge",
+    "esr_conv_packed_floats", "esr_conv_pack", "esr_conv_relu", "esr_maxpool_nhwc", "esr_lpips_layer",
 ]
 
 # full ctypes signatures (argument conversion checked on every call) of the entries that declare them
@@ -240,6 +241,14 @@ SIGNATURES = {
     "esr_flag_scan_bits": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "esr_index_partition_bits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "esr_regroup_stats_merge": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "esr_conv_packed_floats": (C.c_int64, [C.c_int32] * 4),
+    "esr_conv_pack": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "esr_conv_relu": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esr_maxpool_nhwc": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                   C.c_void_p]),
+    "esr_lpips_layer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
 }
 
 

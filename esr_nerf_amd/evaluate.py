@@ -1,6 +1,7 @@
 """Test-view evaluation on the device: the image level of the reference trainers' ``evaluate()``
-(app/fine/fine.py:500-623, app/fine/pdra.py:600-762; the same loop in coarse.py / lts.py) without LPIPS, file writing
-and logging.
+(app/fine/fine.py:500-623, app/fine/pdra.py:600-762; the same loop in coarse.py / lts.py) without file writing and
+logging.  LPIPS is opt-in: ``view_metrics`` / ``evaluate_views`` add ``*/LPIPS_ALEX`` when they are handed an
+``lpips.LpipsAlex`` (the trained weights are the user's to supply).
 
 ``render_camera_view``  one view of a camera set (camera.py): its rays made on the device, then ``render_view``
 ``render_view``       the chunk loop (fine.py:553-570): every chunk's outputs go straight into one set of [H*W, C] buffers
@@ -10,7 +11,7 @@ and logging.
 ``evaluate_views``    the loop over views: per-view lists, their means, PDRA's pooled ``etc/IoU``
 
 Everything stays on the device; a view costs one read-back of its squared-error sums, one per SSIM and one for the IoU
-counts (and the uint8 images when they are asked for).
+counts (and the uint8 images when they are asked for); with LPIPS, one more for its two distances.
 """
 from __future__ import annotations
 
@@ -97,11 +98,14 @@ def postprocess_view(results, white_bg, rgbs=None, hdrs=None, want_u8=False) -> 
 
 
 @torch.no_grad()
-def view_metrics(results, rgbs, hdrs=None, em_mode=None, masks=None, areas=None) -> Dict[str, Optional[float]]:
-    """The metric lines of fine.py:596-609 / pdra.py:710-739 without LPIPS, from post-processed ``results``: ``lin/MSE``,
+def view_metrics(results, rgbs, hdrs=None, em_mode=None, masks=None, areas=None, lpips=None) -> Dict[str, Optional[float]]:
+    """The metric lines of fine.py:596-609 / pdra.py:710-739, from post-processed ``results``: ``lin/MSE``,
     ``lin/PSNR``, ``lin/SSIM``; ``srgb/*`` when the view has an ``srgb/rgb`` image; ``lin/MSE_EXR_off|on`` with ``hdrs``
     and ``em_mode`` (None for the mode the view was not rendered in); ``etc/IoU_I``, ``etc/IoU_U`` with ``masks`` and
-    ``areas``.  MSE is the float64 sum of squared differences over the element count."""
+    ``areas``.  MSE is the float64 sum of squared differences over the element count.  With ``lpips`` (an
+    ``lpips.LpipsAlex``): ``lin/LPIPS_ALEX`` and, when the view has an ``srgb/rgb`` image, ``srgb/LPIPS_ALEX``
+    (pdra.py:615-742) -- the target and the images go through the network as one batch, the target's features are computed
+    once.  Without it the returned keys and values are what they were."""
     sqerr = getattr(results, "sqerr", {})
     pairs = {"lin/MSE": ("lin/rgb_gamma", rgbs)}
     if "srgb/rgb" in results:
@@ -126,6 +130,14 @@ def view_metrics(results, rgbs, hdrs=None, em_mode=None, masks=None, areas=None)
             m[f"{space}/SSIM"] = M.rgb_ssim(results[key], rgbs.reshape(results[key].shape), 1)
     if masks is not None and areas is not None:
         _, m["etc/IoU_I"], m["etc/IoU_U"] = M.IoU(masks, areas.reshape(masks.shape))
+    if lpips is not None:
+        spaces = [(space, key) for space, key in (("lin", "lin/rgb_gamma"), ("srgb", "srgb/rgb")) if key in results]
+        shape = results["lin/rgb_gamma"].shape
+        batch = torch.stack([rgbs.reshape(shape).to(torch.float32)] + [results[key].reshape(shape) for _, key in spaces])
+        feats = lpips.features(batch)
+        host = torch.stack([lpips.distance(feats, 0, 1 + i) for i in range(len(spaces))]).tolist()
+        for (space, _), d in zip(spaces, host):
+            m[f"{space}/LPIPS_ALEX"] = d
     return m
 
 
@@ -136,12 +148,13 @@ def _to(x, device, dtype=None):
 
 @torch.no_grad()
 def evaluate_views(renderer, views: Iterable[dict], batch_size, white_bg, height, width, k_val=None, return_images=False,
-                   device=None, **extra):
+                   device=None, lpips=None, **extra):
     """The view loop of ``evaluate()``.  A view is a dict: ``rays_o``, ``rays_d``, ``viewdirs`` [H*W, 3], ``em_mode``
     (scalar), ``pos_rt`` [3, 3], ``rgbs`` [H*W, 3] and optionally ``hdrs`` [H*W, 3] and ``areas`` [H*W] (bool; with
     ``k_val``: PDRA's emission mask ``any(lin/emit > k_val)`` is applied to ``lin/emit`` and scored against it).
     Returns ``{"metrics": name -> per-view list, "mean": name -> mean over the views that have it, "scene": {"etc/IoU"}
-    when masks were scored, "images": key -> list of uint8 [H, W(, 3)] host arrays with return_images}``."""
+    when masks were scored, "images": key -> list of uint8 [H, W(, 3)] host arrays with return_images}``.  ``lpips``: an
+    ``lpips.LpipsAlex`` adds the ``*/LPIPS_ALEX`` lines of ``view_metrics``."""
     device = torch.device(device) if device is not None else next(renderer.parameters()).device
     metrics: Dict[str, List[Optional[float]]] = {}
     images: Dict[str, list] = {}
@@ -159,7 +172,7 @@ def evaluate_views(renderer, views: Iterable[dict], batch_size, white_bg, height
         areas = _to(view["areas"], device).reshape(height, width) if view.get("areas") is not None else None
         post = postprocess_view(results, white_bg, rgbs=rgbs, hdrs=hdrs, want_u8=return_images)
         m = view_metrics(post, rgbs, hdrs=hdrs, em_mode=view["em_mode"], masks=masks if areas is not None else None,
-                         areas=areas)
+                         areas=areas, lpips=lpips)
         for k in set(metrics) | set(m):
             metrics.setdefault(k, [None] * n_views).append(m.get(k))
         n_views += 1

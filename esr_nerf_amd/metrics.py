@@ -2,6 +2,7 @@
 and ``utils2.image.apply_gamma_curve`` over libesr_hip.so's kernels (esr_nerf_amd/csrc/metrics.hip).
 
 ``rgb_ssim``           the reference's signature; float (or the float64 map as a device tensor with ``return_map``)
+``rgb_lpips``          the reference's signature (AlexNet only), on the model ``set_lpips`` was given (lpips.py)
 ``IoU``                (ratio, intersection, union) of two bool / uint8 masks
 ``loss2psnr``          -10 log10(loss)
 ``apply_gamma_curve``  the sRGB curve in float32
@@ -76,6 +77,39 @@ def rgb_ssim(img0, img1, max_val, filter_size=11, filter_sigma=1.5, k1=0.01, k2=
                                        C.c_double(c1), C.c_double(c2), _lib.ptr(ssim_map), _lib.ptr(scratch),
                                        C.c_void_p(scratch.data_ptr() + 8 * _BLOCKS), _lib.stream_ptr(dev)), "esr_ssim")
         return ssim_map if return_map else float(scratch[_BLOCKS])
+
+
+_LPIPS = {}                   # net_name -> lpips.LpipsAlex (the reference's __LPIPS__, utils2/metric.py:12)
+
+
+def set_lpips(model_or_path, backbone_path=None, device=None):
+    """Give ``rgb_lpips`` its model: an ``lpips.LpipsAlex``, or the path of a state-dict file (``LpipsAlex.from_file``; with
+    ``backbone_path`` the pair of the package's ``alex.pth`` and torchvision's AlexNet).  ``None`` removes it.  Returns the
+    model."""
+    from .lpips import LpipsAlex
+    if model_or_path is None:
+        _LPIPS.pop("alex", None)
+        return None
+    model = model_or_path if isinstance(model_or_path, LpipsAlex) else LpipsAlex.from_file(model_or_path, backbone_path, device)
+    _LPIPS["alex"] = model
+    return model
+
+
+def rgb_lpips(np_gt, np_im, net_name="alex", device=None):
+    """utils2/metric.py:21-28: the LPIPS distance of two [H, W, 3] images in [0, 1] (numpy or tensors), as a float.
+    ``net_name`` "alex" only.  The trained weights are the user's to supply, once, through ``set_lpips``."""
+    if net_name == "vgg":
+        raise NotImplementedError("rgb_lpips: the VGG backbone is not provided, only net_name='alex'")
+    if net_name != "alex":
+        raise ValueError(f"rgb_lpips: unknown net_name {net_name!r}")
+    model = _LPIPS.get("alex")
+    if model is None:
+        raise RuntimeError("rgb_lpips: no LPIPS model is set.  No trained weights travel with this package: call "
+                           "metrics.set_lpips(path) with the state dict of lpips.LPIPS(net='alex') saved by torch.save "
+                           "(or set_lpips(alex_pth, backbone_path=torchvision_alexnet_pth)), or pass an lpips.LpipsAlex")
+    if device is not None and torch.device(device).type == "cuda" and torch.device(device).index not in (None, model.device.index):
+        raise ValueError(f"rgb_lpips: the model lives on {model.device}, not on {device}")
+    return model(np_gt, np_im)
 
 
 def loss2psnr(loss: float):

@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 39
+#define ESR_ABI_VERSION 40
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -1506,6 +1506,67 @@ int esr_index_partition_bits(const int64_t *rows, const uint64_t *words, const i
  * One launch of one wave; `out` may be one of the parts.  n_parts == 0 is success and touches no pointer.
  */
 int esr_regroup_stats_merge(const esr_regroup_stats_t *parts, int64_t n_parts, esr_regroup_stats_t *out, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * Q. LPIPS (AlexNet) image metric -- replaces utils2/metric.py:15-28 (rgb_lpips: lpips.LPIPS(net="alex", version "0.1"),
+ *    normalize=True, eval mode).  Channels-last float32 activations [N,H,W,C]; csrc/lpips.hip.
+ * ------------------------------------------------------------------------- */
+
+#define ESR_CONV_KC 32           /* the reduction index of a packed convolution weight is padded to a multiple of this */
+
+/* floats of a packed [Cout,Cin,kh,kw] weight: roundup(Cin kh kw, ESR_CONV_KC) * Cout; ESR_EINVAL for a size < 1 */
+int64_t esr_conv_packed_floats(int32_t Cout, int32_t Cin, int32_t kh, int32_t kw);
+/*
+ * w [Cout,Cin,kh,kw] f32 (torch's conv2d layout) -> packed [Kp][Cout] f32, the B operand order of v_mfma_f32_32x32x2_f32
+ * (reduction index slowest, output channel on the lane):
+ *   packed[k][n] = w[n][c][ky][kx] for k = (ky kw + kx) Cin + c < Cin kh kw, and 0.0 for the rows up to
+ *   Kp = roundup(Cin kh kw, ESR_CONV_KC)
+ * Once per weight, at load time.  The zero rows are exact: they add fma(0, 0, acc) = acc.  ESR_EINVAL for a NULL pointer
+ * or a size < 1, ESR_ECAP for more than 2^31 packed floats.
+ */
+int esr_conv_pack(const float *w, int32_t Cout, int32_t Cin, int32_t kh, int32_t kw, float *packed, void *stream);
+/*
+ * y = relu(conv2d(x, w, b, stride, padding = pad)) as an implicit GEMM on v_mfma_f32_32x32x2_f32 (f32 operands, f32
+ * accumulation).  x [N,H,W,Cin], y [N,Ho,Wo,Cout] with Ho = (H + 2 pad - kh) / stride + 1 (floor), Wo alike; packed as
+ * esr_conv_pack left it (16-byte aligned); bias [Cout].  GEMM: M = N Ho Wo output pixels, N = Cout, K = Cin kh kw.
+ *
+ * affine (or NULL) [2 Cin] f32 DEVICE memory, shift then scale: the convolution reads s = ((2 x - 1) - shift[c]) / scale[c]
+ * in place of x -- each step a separately rounded binary32 operation, the last a correctly rounded division -- and the
+ * zero padding applies to s, not to x (the scaling layer of LPIPS in front of its first convolution).
+ *
+ * Order of the arithmetic, which the result's bits follow from: per output value ONE chain
+ *   acc = +0;  for k = 0, 1, ... Kp-1 (k = (ky kw + kx) Cin + c, ascending):  acc = fmaf(patch[k], packed[k][n], acc)
+ *   y = acc + bias[n];  y = y > 0 ? y : 0 (NaN stays NaN)
+ * where patch[k] is 0 for a tap outside the image and for k >= K.  No split-K and no atomics: the bits of a value do not
+ * depend on the tile, the image of the batch or the call it is computed in.
+ *
+ * ESR_EINVAL (nothing written): a NULL or (packed) misaligned pointer, Cout % 32 != 0, any size < 1, pad < 0, an empty
+ * output (H + 2 pad < kh or W + 2 pad < kw).  ESR_ECAP (nothing written): x, y or packed with more than 2^31 elements.
+ */
+int esr_conv_relu(const float *x, int32_t N, int32_t H, int32_t W, int32_t Cin, const float *packed, const float *bias,
+                  int32_t Cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad, const float *affine, float *y,
+                  void *stream);
+/*
+ * F.max_pool2d(kernel_size = k, stride = stride), floor mode, no padding, on [N,H,W,C] f32: y [N,Ho,Wo,C] with
+ * Ho = (H - k) / stride + 1.  A NaN in the window gives NaN, as in torch; otherwise bit-equal to torch.  ESR_EINVAL for a
+ * size < 1 or H, W < k; ESR_ECAP for more than 2^31 elements.  (LPIPS's AlexNet: k = 3, stride = 2.)
+ */
+int esr_maxpool_nhwc(const float *x, int32_t N, int32_t H, int32_t W, int32_t C, int32_t k, int32_t stride, float *y,
+                     void *stream);
+/*
+ * One layer's LPIPS term.  f0, f1 [npix,C] f32 (the same tap of the two images), lin_w [C] f32 (the 1x1 "lin" weight):
+ *   per pixel, in binary32:  s_i = sum_c f_i[c]^2,  den_i = sqrtf(s_i) + 1e-10f,  n_i[c] = f_i[c] / den_i,
+ *                            d[c] = n_0[c] - n_1[c]
+ *     (s_i: lane l of the pixel's wave adds c = l, l + 64, ... in that order, product and sum separately rounded, then a
+ *      butterfly over the 64 lanes with offsets 32, 16, ... 1; sqrtf and the divisions correctly rounded)
+ *   in binary64 from there:  out[0] = (sum_pixels sum_c (double)lin_w[c] * ((double)d[c] * (double)d[c])) / npix
+ * A pixel whose features are all zero has n = 0 / 1e-10 = 0: never NaN.  Swapping f0 and f1 gives the same bits, f0 == f1
+ * gives exactly 0.0.  Sums in a fixed order (lane, wave, workgroup, then one workgroup over partials
+ * [ESR_METRICS_BLOCKS] f64): no float atomics, the same bits on every call.  ESR_EINVAL for a NULL pointer, npix < 1 or
+ * C < 1; ESR_ECAP for npix * C > 2^31.
+ */
+int esr_lpips_layer(const float *f0, const float *f1, int64_t npix, int32_t C, const float *lin_w, double *partials,
+                    double *out, void *stream);
 
 #ifdef __cplusplus
 }
