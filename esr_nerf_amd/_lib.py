@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libesr_hip.so")
 # developer experiments only (python -m esr_nerf_amd.build --variant builds alternative libraries; tools/ab_env.sh times them
 # side by side on one box)
 LIB_PATH = os.environ.get("ESR_LIB_PATH", LIB_PATH)
-ABI_VERSION = 40
+ABI_VERSION = 41
 _lib = None
 
 
@@ -197,6 +197,7 @@ EXPORTS = [
     "esr_emit_decide", "esr_emit_decide_bits", "esr_flags_pack", "esr_flags_unpack", "esr_flag_scan_bits",
     "esr_index_partition_bits", "esr_regroup_stats_merge",
     "esr_conv_packed_floats", "esr_conv_pack", "esr_conv_relu", "esr_maxpool_nhwc", "esr_lpips_layer",
+    "esr_raster_faces", "esr_raster_resolve", "esr_source_masks",
 ]
 
 # full ctypes signatures (argument conversion checked on every call) of the entries that declare them
@@ -249,6 +250,12 @@ SIGNATURES = {
                                    C.c_void_p]),
     "esr_lpips_layer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
+    "esr_raster_faces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                   C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                   C.c_void_p]),
+    "esr_raster_resolve": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esr_source_masks": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 40
+#define ESR_ABI_VERSION 41
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -1567,6 +1567,49 @@ int esr_maxpool_nhwc(const float *x, int32_t N, int32_t H, int32_t W, int32_t C,
  */
 int esr_lpips_layer(const float *f0, const float *f1, int64_t npix, int32_t C, const float *lin_w, double *partials,
                     double *out, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * R. Surface rasteriser: the exported mesh z-buffered into camera views (face, depth, source masks).  No reference
+ *    counterpart: the reference reads a view's source masks from the dataset's annotations (data/esrnerf/esrnerf.py
+ *    `areas` / `em_masks`) or renders them (app/fine/pdra.py:684-688)
+ * ------------------------------------------------------------------------- */
+
+/*
+ * Z-buffer of the views [v0, v1) of cam.  vertices [n_vertices,3] f64 (world), triangles [n_faces,3] i64 (an index outside
+ * [0, n_vertices) is the caller's error: such a face reads nothing and covers nothing), w2c [cam.n_views,12] f64: each
+ * view's world-to-camera matrix, row-major 3x4.  All of the following in binary64, each operation rounded on its own:
+ *   p_c = W (p, 1);  a face with ANY vertex at z_c <= z_near is dropped and counted (there is no near-plane clipping);
+ *   u = fx x_c / z_c + cx, v = fy y_c / z_c + cy;  the centre of pixel (i, j) is (i + 0.5, j + 0.5);
+ *   A = (u1 - u0)(v2 - v0) - (v1 - v0)(u2 - u0);  b_k = E_k / A with E_k the same expression on the centre and the other
+ *   two vertices;  covered iff A is finite, A != 0 and every b_k >= 0 (inclusive edges, both windings, no culling);
+ *   z = 1 / ((b_0 / z_0 + b_1 / z_1) + b_2 / z_2), rounded once to binary32.
+ * zbuf u64 [(v1 - v0), height * width] (indexed by view - v0): per pixel the minimum over the covering faces of
+ * (binary32 bits of z) << 32 | face id, all ones where no face covers: the nearest face, on equal binary32 depth the smaller
+ * id; 64-bit atomic minima, so the same bytes on every call.  n_dropped i32 [(v1 - v0)].  Both are cleared first.
+ * A face whose clamped bounding box holds more than big_px pixel centres is rasterised by a whole workgroup instead of one
+ * lane (the same expressions: the words do not depend on big_px).  queue i64 [queue_cap] and queue_count u64 [1] are
+ * workspace; queue_cap >= (v1 - v0) * n_faces, so that no face can be lost (else ESR_ECAP).
+ * ESR_EINVAL: a NULL or misaligned pointer, a bad view range, z_near not in (0, inf), big_px < 0, a negative size;
+ * ESR_ECAP: n_faces or n_vertices >= 2^31.  Nothing is written in either case.  v0 == v1 launches nothing; n_faces == 0
+ * only clears.
+ */
+int esr_raster_faces(const esr_camera_t *cam, const double *w2c, int32_t v0, int32_t v1, const double *vertices,
+                     int64_t n_vertices, const int64_t *triangles, int64_t n_faces, double z_near, int64_t big_px,
+                     uint64_t *zbuf, int32_t *n_dropped, int64_t *queue, int64_t queue_cap, uint64_t *queue_count,
+                     void *stream);
+/* zbuf u64 [n_px] (any number of views) -> face i32 [n_px]: the word's low half, -1 where empty; depth f32 [n_px]: the
+ * word's high half as binary32, +inf where empty.  Plain stores.  ESR_ECAP for n_px >= 2^31. */
+int esr_raster_resolve(const uint64_t *zbuf, int64_t n_px, int32_t *face, float *depth, void *stream);
+/*
+ * Per-view masks of edit conditions from a face image.  face i32 [n_views,n_px] (esr_raster_resolve), face_source i32
+ * [n_faces] (-1: in no source), cond_of_source i32 [n_sources] (-1: in no condition).  masks f32 [n_views,n_cond,n_px]:
+ * 1 where the pixel's face belongs to a source of that condition, else 0 -- every element written; a pixel that is empty,
+ * whose face has no source or whose source has no condition is 0 in every mask.  pixels i64 [n_views,n_sources]: the
+ * visible pixels of every source (integer atomics: exact).  n_cond <= ESR_RELIGHT_MAX_COND (else ESR_ECAP).
+ */
+int esr_source_masks(const int32_t *face, int32_t n_views, int64_t n_px, const int32_t *face_source, int64_t n_faces,
+                     const int32_t *cond_of_source, int32_t n_sources, int32_t n_cond, float *masks, int64_t *pixels,
+                     void *stream);
 
 #ifdef __cplusplus
 }
