@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libesr_hip.so")
 # developer experiments only (python -m esr_nerf_amd.build --variant builds alternative libraries; tools/ab_env.sh times them
 # side by side on one box)
 LIB_PATH = os.environ.get("ESR_LIB_PATH", LIB_PATH)
-ABI_VERSION = 41
+ABI_VERSION = 42
 _lib = None
 
 
@@ -140,6 +140,8 @@ RESAMPLE_MAX_C = 16                     # ESR_RESAMPLE_MAX_C
 DENSITY_BOUNDS_BLOCKS = 1024            # ESR_DENSITY_BOUNDS_BLOCKS
 PARTITION_BLOCK = 1024                  # ESR_PARTITION_BLOCK
 PARTITION_SCAN_TILE = 1024              # ESR_PARTITION_SCAN_TILE
+SIMPLIFY_MAX_C = 16                     # ESR_SIMPLIFY_MAX_C
+SIMPLIFY_DEBUG = 15                     # ESR_SIMPLIFY_DEBUG
 
 
 class EsrRegroupStats(C.Structure):     # esr_regroup_stats_t
@@ -198,6 +200,7 @@ EXPORTS = [
     "esr_index_partition_bits", "esr_regroup_stats_merge",
     "esr_conv_packed_floats", "esr_conv_pack", "esr_conv_relu", "esr_maxpool_nhwc", "esr_lpips_layer",
     "esr_raster_faces", "esr_raster_resolve", "esr_source_masks",
+    "esr_simplify_cell_keys", "esr_simplify_pair_keys", "esr_simplify_clusters", "esr_simplify_face_keys", "esr_simplify_keep",
 ]
 
 # full ctypes signatures (argument conversion checked on every call) of the entries that declare them
@@ -256,6 +259,15 @@ SIGNATURES = {
     "esr_raster_resolve": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "esr_source_masks": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esr_simplify_cell_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "esr_simplify_pair_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "esr_simplify_clusters": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double,
+                                        C.c_double, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "esr_simplify_face_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esr_simplify_keep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                    C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -10,6 +10,8 @@ fine.py:632) and knows emissive sources only per view, as the image masks ``any(
 ``emissive_sources``   a vertex is emissive iff max_c emission > k_val; a face is selected iff its three vertices are;
                        the sources are the connected components of the selected faces (mesh.connected_components: two
                        faces are connected iff they share a vertex) with mesh.component_stats of each
+``simplify_surface``   mesh.simplify / mesh.simplify_to on a Surface: fewer, larger faces with the attributes re-queried
+                       from the model or area-weighted from the old vertices, and the faces' source ids carried along
 ``write_surface_ply``  a binary PLY with the attributes per vertex and the source id per face (chamfer.read_ply reads the
                        mesh back)
 
@@ -93,6 +95,48 @@ def emissive_sources(surface: Surface, k_val: float, min_area: float = 0.0) -> S
                         st["mean_attr"], st["peak"], st["area_centroid"], st["area_attr"])
 
 
+_ATTR_WIDTH = {"normal": 3, "sdf": 1, "basecolor": 3, "roughness": 1, "metallic": 1, "emission": 3}
+
+
+@torch.no_grad()
+def simplify_surface(surface: Surface, cell: Optional[float] = None, target_faces: Optional[int] = None, model=None,
+                     face_source: Optional[torch.Tensor] = None, lam: float = 1e-3, chunk: int = 1 << 18):
+    """The surface simplified by quadric vertex clustering: ``mesh.simplify`` at the cell size ``cell`` (world units) or
+    ``mesh.simplify_to`` at ``target_faces``; exactly one of the two is given.  -> ``(Surface, face_source')``.
+
+    With ``model`` the attributes are queried again at the new vertices (``surface_attributes``, the points clamped to
+    the model's box as ``extract_surface`` clamps them).  Without it they are the area-weighted means of the old
+    vertices' (the 12 channels of ``ATTR_KEYS`` go through the kernel together) and the normals are normalised again.
+    ``face_source`` (int32 [F], ``SourceReport.face_source``) is carried to the kept faces: ``face_source[face_origin]``;
+    None stays None.  The result is a Surface like any other: ``emissive_sources``, ``write_surface_ply``,
+    ``raster.rasterize`` and ``raster.edit_view_data`` take it unchanged."""
+    if (cell is None) == (target_faces is None):
+        raise ValueError("simplify_surface: give exactly one of cell and target_faces")
+    v, t = surface.vertices, surface.triangles
+    if face_source is not None and (not isinstance(face_source, torch.Tensor) or face_source.shape != (t.shape[0],) or
+                                    face_source.device != t.device):
+        raise ValueError("simplify_surface: face_source must have one entry per face, on the surface's device")
+    packed = None
+    if model is None:
+        packed = torch.cat([surface.attrs[k].reshape(v.shape[0], -1).float() for k in ATTR_KEYS], dim=1).contiguous()
+    if cell is not None:
+        nv, nt, na, _, face_origin = mesh.simplify(v, t, cell, lam=lam, attr=packed)
+    else:
+        (nv, nt, na, _, face_origin), _, _ = mesh.simplify_to(v, t, target_faces, lam=lam, attr=packed)
+    if model is None:
+        attrs, at = {}, 0
+        for k in ATTR_KEYS:
+            w = _ATTR_WIDTH[k]
+            attrs[k] = na[:, at:at + w].reshape((-1, 3) if surface.attrs[k].dim() == 2 else (-1,)).contiguous()
+            at += w
+        attrs["normal"] = torch.nn.functional.normalize(attrs["normal"], dim=1)
+    else:
+        lo, hi = (b.to(nv.device) for b in mesh._box(model))
+        got = model.surface_attributes(torch.minimum(torch.maximum(nv.float(), lo), hi), chunk=chunk)
+        attrs = {k: got[k] for k in ATTR_KEYS}
+    return Surface(nv.contiguous(), nt.contiguous(), attrs), None if face_source is None else face_source[face_origin]
+
+
 VERTEX_PROPERTIES = ["x", "y", "z", "nx", "ny", "nz", "basecolor_r", "basecolor_g", "basecolor_b", "roughness", "metallic",
                      "emission_r", "emission_g", "emission_b"]
 
@@ -133,4 +177,5 @@ def write_surface_ply(path, surface: Surface, face_source: Optional[torch.Tensor
         f.write(frec.tobytes())
 
 
-__all__ = ["Surface", "SourceReport", "extract_surface", "emissive_sources", "write_surface_ply", "VERTEX_PROPERTIES"]
+__all__ = ["Surface", "SourceReport", "extract_surface", "emissive_sources", "simplify_surface", "write_surface_ply",
+           "VERTEX_PROPERTIES"]

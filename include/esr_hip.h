@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 41
+#define ESR_ABI_VERSION 42
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -1610,6 +1610,75 @@ int esr_raster_resolve(const uint64_t *zbuf, int64_t n_px, int32_t *face, float 
 int esr_source_masks(const int32_t *face, int32_t n_views, int64_t n_px, const int32_t *face_source, int64_t n_faces,
                      const int32_t *cond_of_source, int32_t n_sources, int32_t n_cond, float *masks, int64_t *pixels,
                      void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * S. Surface simplification by quadric vertex clustering (esr_nerf_amd/mesh.py: simplify).  No reference counterpart:
+ *    the reference hands the raw marching-cubes mesh to trimesh (app/fine/pdra.py:781)
+ * ------------------------------------------------------------------------- */
+
+#define ESR_SIMPLIFY_MAX_C 16     /* most attribute channels per vertex */
+#define ESR_SIMPLIFY_DEBUG 15     /* doubles per cluster of the debug output */
+
+/*
+ * The definition.  Input: vertices [V,3] f64 (finite), triangles [F,3] i64, a cell size h > 0, lam > 0, optionally attr
+ * [V,C] f32 with 1 <= C <= ESR_SIMPLIFY_MAX_C.  All arithmetic is binary64, every operation rounded on its own.
+ *   grid      o = the per-axis minimum of the vertices; the cell of v is floor((v - o) / h) per axis, at most 2^21 - 1
+ *             cells on an axis; a cluster is an occupied cell, clusters are numbered by ascending key x << 42 | y << 21 | z;
+ *             g_k = o + (c_k + 0.5) h is the centre of cluster k's cell.  Everything below uses r = v - g_k (one rounding)
+ *   members   M_k; xbar_k = (sum r) / |M_k|, clamped into the cell box [-h/2, h/2]^3
+ *   faces     I_k = the faces with at least one corner in k, each counted once.  For corners a, b, c:
+ *             n = (b - a) x (c - a) (not normalised: the quadric is weighted by area^2), d = -n . a,
+ *             s = |b - a|^2 |c - a|^2, w = |n| / 2
+ *             A = sum n n^T, b = sum n d, c = sum d d, S = sum s,
+ *             P = sum w sum_{corners of f in k} attr[corner], W = sum w #corners of f in k
+ *   position  S == 0: y = xbar.  Otherwise (A + lam S I) y* = -b + lam S xbar (SPD, condition number <= 1 + 1 / lam as
+ *             tr A <= S), then y = xbar + t (y* - xbar) with the largest t in [0, 1] that keeps y in the box.  The new
+ *             vertex is g_k + y
+ *   attribute float(P / W); for W == 0 the attribute of the member with the smallest id
+ *   faces'    corners -> clusters; a face with two equal corners is dropped; among the faces with the same SET of three
+ *             clusters, whatever their winding, the smallest face id is kept, with its own winding and in its order;
+ *             clusters that no kept face names are dropped and the rest renumbered in ascending order
+ * The sums run in a fixed order (the header of csrc/simplify.hip): no atomics, the same bytes on every call for a fixed
+ * `big`.  Sorting, scanning and allocation are the caller's (torch); the entry points below are the arithmetic.
+ * Every entry: ESR_EINVAL for a NULL or misaligned pointer or a negative size, ESR_ECAP for n_vertices or n_faces >= 2^31;
+ * nothing is launched in either case.  An index outside its array is the caller's error: it is skipped, never followed.
+ */
+
+/* keys i64 [n_vertices] = x << 42 | y << 21 | z of floor((v - origin) / h); origin f64 [3] (device) */
+int esr_simplify_cell_keys(const double *vertices, int64_t n_vertices, const double *origin, double h, int64_t *keys,
+                           void *stream);
+/* vertex_cluster i32 [n_vertices]: the cluster of every vertex.  pairs i64 [3 n_faces]: per corner (cluster << 32 | face),
+ * INT64_MAX for a corner whose cluster an earlier corner of the face has; sorted, they are every cluster's incident faces
+ * by ascending id */
+int esr_simplify_pair_keys(const int64_t *triangles, int64_t n_faces, const int32_t *vertex_cluster, int64_t n_vertices,
+                           int64_t *pairs, void *stream);
+/*
+ * The per-cluster pass: a cluster's sums, mean, solve, clip and attributes in one kernel.  cluster_keys i64 [n_clusters] ascending;
+ * member_ids i64 [n_vertices]: the vertex ids sorted by cluster (stable), member_start i64 [n_clusters + 1] its segments;
+ * pairs i64 [n_pairs]: the sorted pair keys (an INT64_MAX tail may follow the real pairs inside n_pairs: it lies behind
+ * every segment and is never read), pair_start i64 [n_clusters + 1] its segments, clamped to n_pairs.
+ * positions f64 [n_clusters,3]; attr_out f32 [n_clusters,n_attr] (n_attr == 0: attr and attr_out unused); debug f64
+ * [n_clusters,ESR_SIMPLIFY_DEBUG] or NULL: A00 A01 A02 A11 A12 A22, b0 b1 b2, c, S, W, xbar0 xbar1 xbar2.
+ * A cluster of more than `big` (>= 1) pairs or members is summed by a workgroup in a fixed-shape tree instead of one lane
+ * (a second launch of the same call, whose workgroups pass the smaller clusters by).
+ * ESR_EINVAL also for h or lam not in (0, inf), big < 1, n_pairs > 3 n_faces, n_clusters > n_vertices; ESR_ECAP also for
+ * n_attr > ESR_SIMPLIFY_MAX_C.
+ */
+int esr_simplify_clusters(const double *vertices, int64_t n_vertices, const int64_t *triangles, int64_t n_faces,
+                          const int32_t *vertex_cluster, const int64_t *cluster_keys, int64_t n_clusters,
+                          const int64_t *member_start, const int64_t *member_ids, const int64_t *pair_start,
+                          const int64_t *pairs, int64_t n_pairs, const double *origin, double h, double lam,
+                          const float *attr, int32_t n_attr, int64_t big, double *positions, float *attr_out,
+                          double *debug, void *stream);
+/* key_hi i64 [n_faces] = smallest cluster << 32 | middle cluster, INT64_MAX for a face with two equal corners;
+ * key_lo i32 [n_faces] = the largest cluster (0 for a dropped face) */
+int esr_simplify_face_keys(const int64_t *triangles, int64_t n_faces, const int32_t *vertex_cluster, int64_t n_vertices,
+                           int64_t *key_hi, int32_t *key_lo, void *stream);
+/* order i64 [n_faces]: the face ids sorted by (key_hi, key_lo, id).  keep u8 [n_faces] = 1 for the first face of every run
+ * of equal keys that is not INT64_MAX, else 0; used u8 [n_clusters] = 1 for the clusters a kept face names, else 0 */
+int esr_simplify_keep(const int64_t *order, const int64_t *key_hi, const int32_t *key_lo, int64_t n_faces,
+                      const int64_t *triangles, const int32_t *vertex_cluster, int64_t n_vertices, int64_t n_clusters,
+                      uint8_t *keep, uint8_t *used, void *stream);
 
 #ifdef __cplusplus
 }
