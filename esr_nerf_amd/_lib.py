@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libesr_hip.so")
 # developer experiments only (python -m esr_nerf_amd.build --variant builds alternative libraries; tools/ab_env.sh times them
 # side by side on one box)
 LIB_PATH = os.environ.get("ESR_LIB_PATH", LIB_PATH)
-ABI_VERSION = 42
+ABI_VERSION = 43
 _lib = None
 
 
@@ -201,6 +201,7 @@ EXPORTS = [
     "esr_conv_packed_floats", "esr_conv_pack", "esr_conv_relu", "esr_maxpool_nhwc", "esr_lpips_layer",
     "esr_raster_faces", "esr_raster_resolve", "esr_source_masks",
     "esr_simplify_cell_keys", "esr_simplify_pair_keys", "esr_simplify_clusters", "esr_simplify_face_keys", "esr_simplify_keep",
+    "esr_bvh_keys", "esr_bvh_tree", "esr_bvh_fit", "esr_bvh_cast",
 ]
 
 # full ctypes signatures (argument conversion checked on every call) of the entries that declare them
@@ -268,6 +269,12 @@ SIGNATURES = {
     "esr_simplify_face_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "esr_simplify_keep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
                                     C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esr_bvh_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esr_bvh_tree": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esr_bvh_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "esr_bvh_cast": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                               C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -137,6 +137,83 @@ def simplify_surface(surface: Surface, cell: Optional[float] = None, target_face
     return Surface(nv.contiguous(), nt.contiguous(), attrs), None if face_source is None else face_source[face_origin]
 
 
+VISIBILITY_CHUNK = 1 << 22               # most segments of one launch of source_visibility
+
+
+def source_samples(surface: Surface, report: SourceReport, samples: int = 16):
+    """The sample points of every source, fixed by the mesh alone: a source's faces in id order, their cumulative area in
+    float64 (area = 0.5 sqrt((n0 n0 + n1 n1) + n2 n2), n = (b - a) x (c - a)); sample k of n = min(samples, n_faces) is
+    the centre ((a + b) + c) * (1 / 3) of the first face whose cumulative area reaches (k + 1/2) / n of the total.
+    -> (face int32 [S, samples], point float64 [S, samples, 3], n int64 [S]); the slots k >= n of a source are unused."""
+    samples = int(samples)
+    if samples < 1:
+        raise ValueError(f"source_samples: samples must be at least 1, got {samples}")
+    v, t, fs = surface.vertices, surface.triangles, report.face_source
+    dev, S = v.device, len(report)
+    if S == 0 or t.shape[0] == 0:
+        return (torch.zeros(S, samples, dtype=torch.int32, device=dev), torch.zeros(S, samples, 3, dtype=torch.float64, device=dev),
+                torch.zeros(S, dtype=torch.int64, device=dev))
+    key = torch.where(fs < 0, S, fs.long())
+    skey, order = torch.sort(key, stable=True)
+    a, b, c = (v[t[order, k]] for k in range(3))
+    e1, e2 = b - a, c - a
+    # (every product and difference is its own launch: nothing can be contracted into an fma)
+    n0 = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+    n1 = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+    n2 = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+    area = torch.sqrt((n0 * n0 + n1 * n1) + n2 * n2) * 0.5
+    area = torch.where(torch.isfinite(area), area, torch.zeros_like(area))
+    cum = torch.cumsum(area, 0)
+    start = torch.searchsorted(skey, torch.arange(S + 1, dtype=torch.int64, device=dev))
+    zero = torch.zeros(1, dtype=torch.float64, device=dev)
+    edge = torch.cat([zero, cum])[start]                              # the cumulative area before each source's first face
+    base, total = edge[:-1], edge[1:] - edge[:-1]
+    count = start[1:] - start[:-1]
+    n = count.clamp(max=samples)
+    k = torch.arange(samples, dtype=torch.float64, device=dev)
+    thr = base[:, None] + ((k[None, :] + 0.5) / n.clamp(min=1).double()[:, None]) * total[:, None]
+    j = torch.searchsorted(cum, thr.contiguous())
+    j = torch.minimum(torch.maximum(j, start[:-1, None]), (start[1:, None] - 1).clamp(min=0))
+    point = ((a[j] + b[j]) + c[j]) * (1.0 / 3.0)                     # (a product: a device division by a number is not one rounding)
+    return order[j].to(torch.int32), point, n
+
+
+@torch.no_grad()
+def source_visibility(surface: Surface, report: SourceReport, points: torch.Tensor, samples: int = 16, bvh=None,
+                      eps: float = 1e-6) -> torch.Tensor:
+    """float32 [P, S]: for every query point and every source of ``report`` the share of the source's sample points
+    (``source_samples``) the point sees.  A sample is seen iff no face other than the sample's own is hit strictly inside
+    the segment from the point to the sample (``raycast.occluded_segments`` with ``skip_face``).  All P * S * n segments go
+    through the any-hit walk, at most ``VISIBILITY_CHUNK`` per launch; the mean is taken on the device and nothing is read
+    back.  ``bvh``: the ``raycast.Bvh`` of the surface, built here when None."""
+    from . import raycast
+    v = surface.vertices
+    dev, S = v.device, len(report)
+    if not isinstance(points, torch.Tensor) or points.device != dev or points.dim() != 2 or points.shape[1] != 3 or \
+            points.dtype not in (torch.float32, torch.float64):
+        raise ValueError("source_visibility: points must be a float [P, 3] tensor on the surface's device")
+    P = int(points.shape[0])
+    out = torch.zeros(P, S, dtype=torch.float32, device=dev)
+    if P == 0 or S == 0:
+        return out
+    if bvh is None:
+        bvh = raycast.build(v, surface.triangles)
+    face, point, n = source_samples(surface, report, samples)
+    K = face.shape[1]
+    valid = torch.arange(K, device=dev)[None, :] < n[:, None]           # [S, K]
+    pts = points.double()
+    step = max(1, VISIBILITY_CHUNK // (S * K))
+    for p0 in range(0, P, step):
+        p = pts[p0:p0 + step]
+        m = int(p.shape[0])
+        occ = raycast.occluded_segments(bvh, p[:, None, None, :].expand(m, S, K, 3).reshape(-1, 3),
+                                        point[None].expand(m, S, K, 3).reshape(-1, 3),
+                                        skip_face=face[None].expand(m, S, K).reshape(-1), eps=eps).reshape(m, S, K)
+        seen = ((occ == 0) & valid[None]).sum(-1)
+        out[p0:p0 + step] = (seen.double() / n.clamp(min=1).double()[None, :]).float()
+    return out
+
+
 VERTEX_PROPERTIES = ["x", "y", "z", "nx", "ny", "nz", "basecolor_r", "basecolor_g", "basecolor_b", "roughness", "metallic",
                      "emission_r", "emission_g", "emission_b"]
 
@@ -178,4 +255,4 @@ def write_surface_ply(path, surface: Surface, face_source: Optional[torch.Tensor
 
 
 __all__ = ["Surface", "SourceReport", "extract_surface", "emissive_sources", "simplify_surface", "write_surface_ply",
-           "VERTEX_PROPERTIES"]
+           "source_samples", "source_visibility", "VERTEX_PROPERTIES"]

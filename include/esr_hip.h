@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 42
+#define ESR_ABI_VERSION 43
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -1679,6 +1679,90 @@ int esr_simplify_face_keys(const int64_t *triangles, int64_t n_faces, const int3
 int esr_simplify_keep(const int64_t *order, const int64_t *key_hi, const int32_t *key_lo, int64_t n_faces,
                       const int64_t *triangles, const int32_t *vertex_cluster, int64_t n_vertices, int64_t n_clusters,
                       uint8_t *keep, uint8_t *used, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * T. Ray casting against the surface (esr_nerf_amd/raycast.py): a linear BVH over the faces and a nearest-hit / any-hit
+ *    walk.  No reference counterpart: the reference hands the mesh to trimesh (app/fine/pdra.py:781)
+ * ------------------------------------------------------------------------- */
+
+/*
+ * One internal node, 64 bytes: the links and the boxes of its TWO CHILDREN (a step of the walk reads one record).
+ *   box[k]    child k's box, binary32, lo x y z then hi x y z, rounded outward: every float64 coordinate of every vertex
+ *             below the child lies in [lo, hi].  An empty box is lo = +inf, hi = -inf
+ *   child[k]  >= 0: an internal node; < 0: a leaf, and ~child[k] is its face id.  Leaves have no record of their own
+ *   parent    2 * (the parent's index) + (which child of it this node is); -1 for the root, node 0
+ *   pad       0
+ * A mesh of F >= 2 faces has F - 1 nodes and F leaves, one face each; F == 1 has no node (the one face is the tree).
+ */
+typedef struct __attribute__((aligned(16))) esr_bvh_node {
+    float box[2][6];
+    int32_t child[2];
+    int32_t parent;
+    int32_t pad;
+} esr_bvh_node_t;
+
+/*
+ * Conventions of this section.  vertices [n_vertices,3] f64, triangles [n_faces,3] i64 (a face that names a vertex outside
+ * [0, n_vertices) reads nothing and is never hit).  Every entry: a size of 0 succeeds and touches no pointer; ESR_EINVAL
+ * for a negative size or a NULL or misaligned pointer (f64 / i64: 8 bytes, nodes: 16, the rest: 4); ESR_ECAP for a size
+ * >= 2^31; nothing is launched in either case.  Everything is enqueued on `stream`, nothing waits on the host.  Sorting and
+ * allocation are the caller's (torch).  The same input gives the same bytes on every call.
+ */
+
+/*
+ * Per face f, all in binary64, each operation rounded on its own:
+ *   lo, hi = the per-axis minimum / maximum of the three vertices;  boxes f32 [n_faces,6] = lo rounded DOWN to binary32,
+ *   hi rounded UP (the nearest binary32, stepped once by nextafter where that lies on the wrong side)
+ *   per axis  c = 0.5 lo + 0.5 hi,  ext = scene_hi - scene_lo,
+ *             cell = ext > 0 ? floor(((c - scene_lo) / ext) * 2097152) : 0, clamped to [0, 2^21 - 1]
+ *   keys i64 [n_faces] = the Morton code of the cells: bit k of cell x is bit 3 k + 2, of y 3 k + 1, of z 3 k (63 bits)
+ * scene_box f64 [6] (device): lo x y z, hi x y z of the mesh's finite vertices.  A face with a vertex that is not finite
+ * (or outside the vertex array) gets the key 2^63 - 1 and the empty box.
+ */
+int esr_bvh_keys(const double *vertices, int64_t n_vertices, const int64_t *triangles, int64_t n_faces,
+                 const double *scene_box, int64_t *keys, float *boxes, void *stream);
+/*
+ * The binary radix tree (Karras 2012) over sorted_keys i64 [n_faces] ascending; order i64 [n_faces] is the face id at
+ * every sorted position.  Position i stands for the 95-bit string (key, i): equal keys differ in their position.  Node i
+ * covers the largest range of positions around i whose strings share a longer prefix than with the position just outside;
+ * it splits where the first differing bit changes; a child that is one position is a leaf.  The left child (0) holds the
+ * smaller positions.  Writes child, parent and pad of nodes [n_faces - 1] (not the boxes) and leaf_parent i32 [n_faces]: the
+ * `parent` word of every leaf, by sorted position.  One lane per node.  n_faces < 2 writes nothing.
+ */
+int esr_bvh_tree(const int64_t *sorted_keys, const int64_t *order, int64_t n_faces, esr_bvh_node_t *nodes,
+                 int32_t *leaf_parent, void *stream);
+/*
+ * The boxes of the nodes, bottom-up: one lane per leaf stores its box (boxes [order[i]]) in its parent's record, fences
+ * (device scope) and counts itself at the parent; the first to arrive ends, the second takes the union of the two boxes
+ * and climbs on.  No lane waits for another.  Minimum and maximum are exact, so the bytes do not depend on the order of
+ * arrival.  counters i32 [n_faces - 1] is workspace, zeroed by the call; root_box f32 [6] receives the box of the whole tree
+ * (n_faces == 1: the face's box).
+ */
+int esr_bvh_fit(esr_bvh_node_t *nodes, const int32_t *leaf_parent, const int64_t *order, const float *boxes,
+                int64_t n_faces, int32_t *counters, float *root_box, void *stream);
+/*
+ * Rays against the mesh through the tree, one lane per ray.  rays_o, rays_d f64 [n_rays,3]; d is not normalised and t is in
+ * units of d.  t_min, t_max f64 [n_rays] or NULL (then t_min_all / t_max_all for every ray); skip_face i32 [n_rays] or NULL:
+ * a face the ray never hits (-1: none).  The triangle test, binary64, every operation rounded on its own, in this order:
+ *   e1 = b - a, e2 = c - a, p = d x e2, det = (e1.x p.x + e1.y p.y) + e1.z p.z, s = o - a, q = s x e1
+ *   u = ((s.x p.x + s.y p.y) + s.z p.z) / det, v = ((d.x q.x + d.y q.y) + d.z q.z) / det,
+ *   t = ((e2.x q.x + e2.y q.y) + e2.z q.z) / det, w = (1 - u) - v;   (x x y).x = x.y y.z - x.z y.y, and cyclically
+ *   a hit iff det is finite and not 0, u >= 0, v >= 0, w >= 0 and t_min < t <= t_max (both windings; a face of zero area
+ *   or one the ray lies in has det == 0)
+ * any_hit == 0: face i32 [n_rays] = the face of the smallest t, among equal t the smallest id, -1 for none; t f64 [n_rays]
+ * (+inf for none); bary f64 [n_rays,2] = u, v (0 for none): the weights of the face's second and third vertex.  The answer
+ * does not depend on the order of the walk: a box is entered when its entry distance is <= the best t so far.
+ * any_hit == 1: hit u8 [n_rays] = 1 iff some face is hit; the walk ends at the first.  (The outputs of the other mode are
+ * unused and may be NULL.)  stats i32 [n_rays,2] or NULL: boxes tested, triangles tested.
+ * A ray with a component of o or d that is not finite hits nothing, and so does one whose interval has a NaN end.  A
+ * component of d that is 0 only asks whether o lies between the box's corners on that axis.
+ * The walk keeps no stack: one bit per level (which child was entered first) in two registers covers the 63 + 31 levels
+ * the tree can have, and parent links lead back up.
+ */
+int esr_bvh_cast(const esr_bvh_node_t *nodes, int64_t n_faces, const double *vertices, int64_t n_vertices,
+                 const int64_t *triangles, const double *rays_o, const double *rays_d, int64_t n_rays,
+                 const double *t_min, const double *t_max, double t_min_all, double t_max_all, const int32_t *skip_face,
+                 int32_t any_hit, int32_t *face, double *t, double *bary, uint8_t *hit, int32_t *stats, void *stream);
 
 #ifdef __cplusplus
 }
