@@ -13,7 +13,7 @@
 //   esr_brick_unpack  scatter the reduced bricks back (negative indices are skipped)
 // All three are pure HBM streams (16-B accesses, one 32-lane group per brick); the union of the flags
 // over ranks and the brick list come from torch.distributed / torch (esr_nerf_amd/grad_sync.py).
-#include "esr_common.h"
+#include "esr_collectives.h"
 
 namespace {
 
@@ -83,29 +83,6 @@ __global__ void __launch_bounds__(256) brick_move_kernel(float *__restrict__ g, 
 // idx[rank] = brick for rank < cap; slots [total, cap) get -1; workgroup 0 publishes the total.
 constexpr int LIST_BLOCKS = 256, LIST_THREADS = 256;
 
-__device__ __forceinline__ int block_scan_excl(int v, int *tmp, int &total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int u = __shfl_up(inc, off);
-        if (lane >= off) inc += u;
-    }
-    if (lane == 63) tmp[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < LIST_THREADS / 64; ++k) {
-        const int t = tmp[k];
-        if (k < w) base += t;
-        tot += t;
-    }
-    __syncthreads();
-    total = tot;
-    return base + inc - v;
-}
-
 __global__ void __launch_bounds__(LIST_THREADS) brick_count_kernel(const uint8_t *__restrict__ flags, int64_t nb,
                                                                    int *__restrict__ counts)
 {
@@ -116,7 +93,7 @@ __global__ void __launch_bounds__(LIST_THREADS) brick_count_kernel(const uint8_t
     int c = 0;
     for (int64_t i = lo; i < hi; ++i) c += flags[i] != 0;
     int total;
-    block_scan_excl(c, tmp, total);
+    esr_block_scan_excl<LIST_THREADS>(c, tmp, total);
     if (threadIdx.x == 0) counts[blockIdx.x] = total;
 }
 
@@ -130,7 +107,7 @@ __global__ void __launch_bounds__(LIST_THREADS) brick_list_kernel(const uint8_t 
     {
         const int c = counts[threadIdx.x];                  // LIST_BLOCKS == LIST_THREADS
         int tot;
-        const int ex = block_scan_excl(c, tmp, tot);
+        const int ex = esr_block_scan_excl<LIST_THREADS>(c, tmp, tot);
         __shared__ int base_s;
         if (threadIdx.x == blockIdx.x) base_s = ex;
         __syncthreads();
@@ -143,7 +120,7 @@ __global__ void __launch_bounds__(LIST_THREADS) brick_list_kernel(const uint8_t 
     int c = 0;
     for (int64_t i = lo; i < hi; ++i) c += flags[i] != 0;
     int total;
-    int64_t r = mine + block_scan_excl(c, tmp, total);
+    int64_t r = mine + esr_block_scan_excl<LIST_THREADS>(c, tmp, total);
     for (int64_t i = lo; i < hi; ++i)
         if (flags[i]) {
             if (r < cap) idx[r] = i;

@@ -21,6 +21,7 @@
 //                        reduction, one LDS slot per wave, one 6-float partial per workgroup; camera_bounds_final_kernel
 //                        folds the partials in one workgroup.
 #include "camera_ray.h"
+#include "esr_collectives.h"
 
 #include <math.h>
 
@@ -144,35 +145,6 @@ __global__ void __launch_bounds__(CAM_THREADS) camera_batch_kernel(BatchParams P
 }
 
 // ---- bounds ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void wave_minmax(float lo[3], float hi[3])
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = fminf(lo[a], __shfl_xor(lo[a], off, ESR_WAVE));
-            hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], off, ESR_WAVE));
-        }
-}
-
-// one 6-float result per workgroup from per-lane running values: wave reduction, then the workgroup's waves through LDS
-__device__ __forceinline__ void block_minmax_store(float lo[3], float hi[3], float *__restrict__ out6)
-{
-    __shared__ float part[CAM_THREADS / ESR_WAVE][6];
-    wave_minmax(lo, hi);
-    const int wave = threadIdx.x >> 6;
-    if (esr_lane() == 0)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { part[wave][a] = lo[a]; part[wave][3 + a] = hi[a]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float v = part[0][threadIdx.x];
-        for (int w = 1; w < CAM_THREADS / ESR_WAVE; ++w)
-            v = threadIdx.x < 3 ? fminf(v, part[w][threadIdx.x]) : fmaxf(v, part[w][threadIdx.x]);
-        out6[threadIdx.x] = v;
-    }
-}
-
 __global__ void __launch_bounds__(CAM_THREADS) camera_bounds_kernel(esr_camera_t cam, const float *__restrict__ poses,
                                                                     float near_, float far_, float *__restrict__ partials)
 {
@@ -191,20 +163,13 @@ __global__ void __launch_bounds__(CAM_THREADS) camera_bounds_kernel(esr_camera_t
             hi[a] = fmaxf(hi[a], fmaxf(pn, pf));
         }
     }
-    block_minmax_store(lo, hi, partials + 6 * blockIdx.x);
+    esr_block_minmax3_store<CAM_THREADS>(lo, hi, partials + 6 * blockIdx.x);
 }
 
 __global__ void __launch_bounds__(CAM_THREADS) camera_bounds_final_kernel(const float *__restrict__ partials, int n_partials,
                                                                           float *__restrict__ out)
 {
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int b = threadIdx.x; b < n_partials; b += CAM_THREADS)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = fminf(lo[a], partials[6 * b + a]);
-            hi[a] = fmaxf(hi[a], partials[6 * b + 3 + a]);
-        }
-    block_minmax_store(lo, hi, out);
+    esr_minmax3_partials<CAM_THREADS>(partials, n_partials, out);
 }
 
 bool camera_ok(const esr_camera_t *cam)

@@ -178,13 +178,6 @@ __global__ void __launch_bounds__(256) coarse_feat_bwd_kernel(CoarseParams P)
     }
 }
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // rgb = sigmoid(z_off) + [on] sigmoid(z_emo); srgb[ray] += w * rgb (segmented reduction over sorted rays)
 __global__ void __launch_bounds__(256) coarse_shade_fwd_kernel(const float *__restrict__ z_off,
                                                                const float *__restrict__ z_emo,

@@ -19,7 +19,7 @@
 // current cell in registers.  When the next sample lies in another cell, only the corners the two cells do not share
 // are added to the grid (global float atomics); the shared ones move to their place in the new cell.  At 0.5 voxel per
 // step a sample changes cell about 0.8 times, so a sample costs ~3 corner adds instead of 8.
-#include "esr_common.h"
+#include "esr_collectives.h"
 
 #define DVGO_BLOCK 256
 #define DVGO_WAVES (DVGO_BLOCK / ESR_WAVE)
@@ -259,13 +259,6 @@ __device__ __forceinline__ void wave_suffix_affine(float &A, float &B)
     B = lane == ESR_WAVE - 1 ? 0.f : Bn;
 }
 
-__device__ __forceinline__ float wave_sum(float x)
-{
-#pragma unroll
-    for (int off = ESR_WAVE / 2; off > 0; off >>= 1) x += __shfl_xor(x, off, ESR_WAVE);
-    return x;
-}
-
 // per-ray set-up shared by the three ray kernels
 struct DvgoRay {
     float o[3], d[3], tmin, nrm, u;
@@ -366,10 +359,10 @@ __global__ void __launch_bounds__(DVGO_BLOCK) dvgo_fwd_kernel(esr_dvgo_t P, esr_
             else O.alphainv_cum[r * (S + 1) + S] = T;
         }
         for (int c = 0; c < 3; ++c) {
-            acc_off[c] = wave_sum(acc_off[c]);
-            if (EVAL) acc_emo[c] = wave_sum(acc_emo[c]);
+            acc_off[c] = esr_wave_sum(acc_off[c]);
+            if (EVAL) acc_emo[c] = esr_wave_sum(acc_emo[c]);
         }
-        if (EVAL) acc_depth = wave_sum(acc_depth);
+        if (EVAL) acc_depth = esr_wave_sum(acc_depth);
         // the lane that owns the last sample holds white_bg; every lane holds the sums
         if (EVAL) {
             const float wb = __shfl(T, (S - 1) / K, ESR_WAVE);

@@ -20,7 +20,7 @@
 //   density_bounds_kernel  the same lookup on the alphamask density; per-lane running min / max of the active coordinates,
 //                          xor-shuffle wave reduction, one 6-float partial per workgroup, a final one-workgroup pass
 //                          (esr_camera_bounds' scheme); the count as above.
-#include "esr_common.h"
+#include "esr_collectives.h"
 
 #include <math.h>
 
@@ -176,34 +176,6 @@ __global__ void __launch_bounds__(GS_THREADS) nonempty_mask_kernel(NodeParams P)
     block_count_add(cnt, P.count_out);
 }
 
-__device__ __forceinline__ void wave_minmax(float lo[3], float hi[3])
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = fminf(lo[a], __shfl_xor(lo[a], off, ESR_WAVE));
-            hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], off, ESR_WAVE));
-        }
-}
-
-__device__ __forceinline__ void block_minmax_store(float lo[3], float hi[3], float *__restrict__ out6)
-{
-    __shared__ float part[GS_THREADS / ESR_WAVE][6];
-    wave_minmax(lo, hi);
-    const int wave = threadIdx.x >> 6;
-    if (esr_lane() == 0)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { part[wave][a] = lo[a]; part[wave][3 + a] = hi[a]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        float v = part[0][threadIdx.x];
-        for (int w = 1; w < GS_THREADS / ESR_WAVE; ++w)
-            v = threadIdx.x < 3 ? fminf(v, part[w][threadIdx.x]) : fmaxf(v, part[w][threadIdx.x]);
-        out6[threadIdx.x] = v;
-    }
-}
-
 __global__ void __launch_bounds__(GS_THREADS) density_bounds_kernel(NodeParams P)
 {
     const int64_t n = (int64_t)P.n[0] * P.n[1] * P.n[2];
@@ -220,21 +192,14 @@ __global__ void __launch_bounds__(GS_THREADS) density_bounds_kernel(NodeParams P
             hi[a] = active ? fmaxf(hi[a], p[a]) : hi[a];
         }
     }
-    block_minmax_store(lo, hi, P.part + 6 * blockIdx.x);
+    esr_block_minmax3_store<GS_THREADS>(lo, hi, P.part + 6 * blockIdx.x);
     block_count_add(cnt, P.count_out);
 }
 
 __global__ void __launch_bounds__(GS_THREADS) density_bounds_final_kernel(const float *__restrict__ partials, int n_partials,
                                                                           float *__restrict__ out)
 {
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int b = threadIdx.x; b < n_partials; b += GS_THREADS)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = fminf(lo[a], partials[6 * b + a]);
-            hi[a] = fmaxf(hi[a], partials[6 * b + 3 + a]);
-        }
-    block_minmax_store(lo, hi, out);
+    esr_minmax3_partials<GS_THREADS>(partials, n_partials, out);
 }
 
 bool dims_ok(int64_t a, int64_t b, int64_t c, int64_t per_cell = 1)

@@ -28,7 +28,7 @@
 // Order: every output value is ONE k-ascending chain of fused multiply-adds from +0 (the instruction's own k order is
 // k0 then k1), bias and ReLU behind it; no split-K, no atomics.  The grid is capped (CV_MAX_BLOCKS resident workgroups)
 // and walks the tiles with a stride, channel tiles of one pixel tile adjacent so that they share the patch in L2.
-#include "esr_common.h"
+#include "esr_collectives.h"
 
 #pragma clang fp contract(off)
 
@@ -190,29 +190,6 @@ __global__ __launch_bounds__(LP_THREADS) void maxpool_nhwc_kernel(const float *_
     }
 }
 
-// sum of the workgroup's `v` (fixed tree: the same bits on every run); red [LP_THREADS]
-__device__ __forceinline__ double lp_block_sum(double v, double *red)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = LP_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = red[tid] + red[tid + s];
-        __syncthreads();
-    }
-    return red[0];
-}
-
-// the wave's sum of `v` in every lane: a butterfly, each step one commutative addition, so all lanes hold the same bits
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off, 64);
-    return v;
-}
-
 // one wave per pixel, lanes over the channels
 __global__ __launch_bounds__(LP_THREADS) void lpips_layer_kernel(const float *__restrict__ f0, const float *__restrict__ f1,
                                                                  int64_t npix, int C, const float *__restrict__ lin_w,
@@ -230,13 +207,13 @@ __global__ __launch_bounds__(LP_THREADS) void lpips_layer_kernel(const float *__
             s0 = s0 + u * u;
             s1 = s1 + v * v;
         }
-        const float den0 = sqrtf(wave_sum(s0)) + 1e-10f, den1 = sqrtf(wave_sum(s1)) + 1e-10f;
+        const float den0 = sqrtf(esr_wave_sum(s0)) + 1e-10f, den1 = sqrtf(esr_wave_sum(s1)) + 1e-10f;
         for (int c = lane; c < C; c += 64) {
             const float d = __fdiv_rn(a[c], den0) - __fdiv_rn(b[c], den1);
             acc = acc + (double)lin_w[c] * ((double)d * (double)d);
         }
     }
-    const double s = lp_block_sum(acc, red);
+    const double s = esr_block_sum_tree<LP_THREADS>(acc, red);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 
@@ -244,11 +221,7 @@ __global__ __launch_bounds__(LP_THREADS) void lpips_layer_kernel(const float *__
 __global__ __launch_bounds__(LP_THREADS) void lp_sum_partials_kernel(const double *__restrict__ partials, int n, double div,
                                                                      double *__restrict__ out)
 {
-    __shared__ double red[LP_THREADS];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < n; i += LP_THREADS) acc = acc + partials[i];
-    const double s = lp_block_sum(acc, red);
-    if (threadIdx.x == 0) out[0] = s / div;
+    esr_sum_partials<LP_THREADS>(partials, n, div, out);
 }
 
 constexpr int64_t LP_CAP = (int64_t)1 << 31;

@@ -18,7 +18,7 @@
 //  * The light-transport combine works on one workgroup per surface point: its R secondary
 //    rays sit on the lanes, the hemisphere means are LDS block reductions, and the 48-lobe
 //    environment-map parameter gradients are reduced per workgroup before touching HBM.
-#include "esr_common.h"
+#include "esr_collectives.h"
 
 namespace {
 
@@ -370,8 +370,7 @@ __device__ __forceinline__ Disney disney_eval(const float a[3], float ro, float 
 
 __device__ __forceinline__ float block_sum(float v, float *scratch)
 {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    v = esr_wave_sum(v);
     const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     __syncthreads();
     if ((threadIdx.x & 63) == 0) scratch[wave] = v;
@@ -498,9 +497,7 @@ __global__ void __launch_bounds__(256) lts_combine_kernel(LtsParams L)
 #pragma unroll
                     for (int k = 0; k < 3; ++k) v[4 + k] = dd * wi[k];
 #pragma unroll
-                    for (int q = 0; q < 7; ++q)
-#pragma unroll
-                        for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_xor(v[q], off);
+                    for (int q = 0; q < 7; ++q) v[q] = esr_wave_sum(v[q]);
                     if (lane == 0) {
 #pragma unroll
                         for (int k = 0; k < 3; ++k) atomicAdd(&acc_mu[3 * j + k], v[k]);

@@ -21,7 +21,7 @@
 // neighbouring lanes' reads, so HBM sees each field value about once per pass.  Bytes per lattice node: the field writes
 // 4; count and each of the two emit passes read 4 (plus 4 written and, per surface triangle, up to 12 gathered of the
 // per-node vertex ids), and the outputs add 24 per vertex and 24 per triangle.
-#include "esr_common.h"
+#include "esr_collectives.h"
 #include "mc_table.h"
 
 namespace {
@@ -95,30 +95,6 @@ __device__ __forceinline__ NodeClass classify(const Lattice &L, uint32_t n)
 
 __device__ __forceinline__ int ntri_of(const NodeClass &c) { return c.ncase < 0 ? 0 : ESR_MC_NTRI[c.ncase]; }
 
-// exclusive scan of one int per lane over the block; `total` = the block's sum
-__device__ __forceinline__ int block_scan_excl(int v, int *tmp, int &total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(inc, off);
-        if (lane >= off) inc += t;
-    }
-    if (lane == 63) tmp[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < MESH_THREADS / 64; ++k) {
-        const int t = tmp[k];
-        if (k < w) base += t;
-        tot += t;
-    }
-    __syncthreads();
-    total = tot;
-    return base + inc - v;
-}
-
 // block b's vertex and triangle totals -> counts[b], counts[nb + b]
 __global__ void __launch_bounds__(MESH_THREADS) mesh_count_kernel(Lattice L, uint32_t nb, int64_t *__restrict__ counts)
 {
@@ -130,7 +106,7 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_count_kernel(Lattice L, uin
         packed = __popc(c.cmask) | ntri_of(c) << 16;
     }
     int total;
-    block_scan_excl(packed, tmp, total);
+    esr_block_scan_excl<MESH_THREADS>(packed, tmp, total);
     if (threadIdx.x == 0) {
         counts[blockIdx.x] = total & 0xffff;
         counts[nb + blockIdx.x] = total >> 16;
@@ -147,7 +123,7 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_emit_vertices_kernel(Lattic
     NodeClass c = {0, -1, 0, 0, 0};
     if (n < nn) c = classify(L, n);
     int total;
-    const int local = block_scan_excl(__popc(c.cmask), tmp, total);
+    const int local = esr_block_scan_excl<MESH_THREADS>(__popc(c.cmask), tmp, total);
     if (n >= nn) return;
     int64_t id = offsets[blockIdx.x] + local;
     vid[n] = (int32_t)id;                                      // the host checks that every vertex id fits 31 bits
@@ -193,7 +169,7 @@ __global__ void __launch_bounds__(MESH_THREADS) mesh_emit_triangles_kernel(Latti
     if (n < nn) c = classify(L, n);
     const int nt = ntri_of(c);
     int total;
-    const int local = block_scan_excl(nt, tmp, total);
+    const int local = esr_block_scan_excl<MESH_THREADS>(nt, tmp, total);
     if (!nt) return;
     int64_t *out = tris + 3 * (offsets[nb + blockIdx.x] + local);
     for (int t = 0; t < 3 * nt; ++t) {

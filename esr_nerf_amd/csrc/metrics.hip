@@ -24,7 +24,7 @@
 // float columns: the float64 planes are read and written at stride 1 (no bank conflict), the staged floats at stride 1
 // with a row change every 24 lanes.  The mean is deterministic: a lane adds its values in a fixed order, the workgroup
 // reduces by a fixed tree into partials[workgroup], and a second launch of one workgroup sums the partials the same way.
-#include "esr_common.h"
+#include "esr_collectives.h"
 
 #pragma clang fp contract(off)
 
@@ -38,21 +38,6 @@ constexpr int SSIM_TC = SSIM_TW * 3;        // float columns of a tile
 struct SsimTaps {
     double t[ESR_SSIM_MAX_TAPS];
 };
-
-// sum of the workgroup's `v` in lane 0 (fixed tree: the same bits on every run); red [MT_THREADS]
-__device__ __forceinline__ double block_sum(double v, double *red)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int s = MT_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] = red[tid] + red[tid + s];
-        __syncthreads();
-    }
-    return red[0];
-}
 
 __device__ __forceinline__ double ssim_value(double mu0, double mu1, double e00, double e11, double e01, double c1, double c2)
 {
@@ -145,7 +130,7 @@ __global__ __launch_bounds__(MT_THREADS) void ssim_kernel(const float *__restric
             acc = acc + v;
         }
     }
-    const double s = block_sum(acc, red);
+    const double s = esr_block_sum_tree<MT_THREADS>(acc, red);
     if (tid == 0) partials[blockIdx.x] = s;
 }
 
@@ -153,11 +138,7 @@ __global__ __launch_bounds__(MT_THREADS) void ssim_kernel(const float *__restric
 __global__ __launch_bounds__(MT_THREADS) void sum_partials_kernel(const double *__restrict__ partials, int n, double div,
                                                                   double *__restrict__ out)
 {
-    __shared__ double red[MT_THREADS];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < n; i += MT_THREADS) acc = acc + partials[i];
-    const double s = block_sum(acc, red);
-    if (threadIdx.x == 0) out[0] = s / div;
+    esr_sum_partials<MT_THREADS>(partials, n, div, out);
 }
 
 // utils2/image.py:14-26 in float32, as torch evaluates it: x <= 0.0031308 ? 12.92 x : 1.055 x^(1/2.4) - 0.055
@@ -197,11 +178,11 @@ __global__ __launch_bounds__(MT_THREADS) void view_post_kernel(esr_view_post_t p
         }
     }
     if (p.target_out) {
-        const double s = block_sum(e_out, red);
+        const double s = esr_block_sum_tree<MT_THREADS>(e_out, red);
         if (threadIdx.x == 0) p.partials[blockIdx.x] = s;
     }
     if (p.target_gamma) {
-        const double s = block_sum(e_gamma, red);
+        const double s = esr_block_sum_tree<MT_THREADS>(e_gamma, red);
         if (threadIdx.x == 0) p.partials[ESR_METRICS_BLOCKS + blockIdx.x] = s;
     }
 }
@@ -213,7 +194,7 @@ __global__ __launch_bounds__(MT_THREADS) void sqerr_kernel(const float *__restri
     double e = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * MT_THREADS)
         e = e + sq_diff(a[i], b[i]);
-    const double s = block_sum(e, red);
+    const double s = esr_block_sum_tree<MT_THREADS>(e, red);
     if (threadIdx.x == 0) partials[blockIdx.x] = s;
 }
 

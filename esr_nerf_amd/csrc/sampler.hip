@@ -7,7 +7,7 @@
 // finds its ray by binary search in the L2-resident inclusive scan -- no
 // scatter-ones + cumsum pass over `total` elements, and the 3 coordinate stores
 // of 64 consecutive samples are contiguous (768 B per wave instruction).
-#include "esr_common.h"
+#include "esr_collectives.h"
 
 namespace {
 
@@ -185,13 +185,7 @@ __global__ void __launch_bounds__(256) segment_sum_kernel(const float *__restric
         const int seg_next = __shfl_down(seg, 1);
         const bool tail = ok && (lane == 63 || seg_next != seg);
         for (int ch = 0; ch < c; ++ch) {
-            float v = ok ? src[i * c + ch] : 0.f;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                float u = __shfl_up(v, off);
-                int su = __shfl_up(seg, off);
-                if (lane >= off && su == seg) v += u;
-            }
+            const float v = esr_wave_segscan_add(ok ? src[i * c + ch] : 0.f, seg, lane);
             if (tail) atomicAdd(&out[(int64_t)seg * c + ch], v);
         }
     }

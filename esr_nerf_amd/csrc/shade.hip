@@ -10,7 +10,7 @@
 // consecutive addresses on every access.  Compositing reduces inside the wave with a
 // segmented shuffle scan (samples are sorted by ray) and issues one float atomic per
 // (ray segment, channel) -- the MI355X replacement of torch_scatter.segment_coo.
-#include "esr_common.h"
+#include "esr_collectives.h"
 
 namespace {
 
@@ -48,18 +48,6 @@ __global__ void __launch_bounds__(256) tone_in_fwd_kernel(const float *__restric
     }
 }
 
-// segmented inclusive scan over the 64 lanes (segments = runs of equal key)
-__device__ __forceinline__ float seg_scan(float v, int key, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const float u = __shfl_up(v, off);
-        const int ku = __shfl_up(key, off);
-        if (lane >= off && ku == key) v += u;
-    }
-    return v;
-}
-
 __global__ void __launch_bounds__(256) composite_fwd_kernel(const float *__restrict__ zt,
                                                             const float *__restrict__ lin,
                                                             const int32_t *__restrict__ rec_ray,
@@ -88,8 +76,8 @@ __global__ void __launch_bounds__(256) composite_fwd_kernel(const float *__restr
                 rgb[z4 + c * 32] = col;
                 l = lin[z4 + c * 32];
             }
-            const float a = seg_scan(w * col, ray, lane);
-            const float b = seg_scan(w * l, ray, lane);
+            const float a = esr_wave_segscan_add(w * col, ray, lane);
+            const float b = esr_wave_segscan_add(w * l, ray, lane);
             if (tail) {
                 atomicAdd(&srgb_marched[3 * ray + c], a);
                 atomicAdd(&lin_marched[3 * ray + c], b);
@@ -163,13 +151,6 @@ __global__ void __launch_bounds__(256) tone_in_bwd_kernel(
     }
 }
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 __global__ void __launch_bounds__(256) loss_kernel(const float *__restrict__ srgb_m,
                                                    const float *__restrict__ lin_m,
                                                    const float *__restrict__ last,
@@ -217,7 +198,7 @@ __global__ void __launch_bounds__(256) loss_kernel(const float *__restrict__ srg
         }
         g_last[r] = gl;
     }
-    acc = wave_sum(acc);
+    acc = esr_wave_sum(acc);
     if (esr_lane() == 0 && acc != 0.f) atomicAdd(loss, acc);
 }
 
@@ -247,7 +228,7 @@ __global__ void __launch_bounds__(256) pair_loss_kernel(const float *__restrict_
     // one atomic per WORKGROUP (and at most 256 workgroups: see the launch): same-address float atomics serialise in the
     // L2 -- one per wave of a 1500-workgroup grid made this kernel 35 us at C4
     __shared__ float part[4];
-    acc = wave_sum(acc);
+    acc = esr_wave_sum(acc);
     if (esr_lane() == 0) part[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -392,7 +373,7 @@ __global__ void __launch_bounds__(256) pair_loss_batch_kernel(PairBatch B)
         if (J.gb) J.gb[i] = -J.w_b * g;
     }
     __shared__ float part[4];
-    acc = wave_sum(acc);
+    acc = esr_wave_sum(acc);
     if (esr_lane() == 0) part[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -421,7 +402,7 @@ __global__ void __launch_bounds__(256) composite3_fwd_kernel(const float *__rest
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float x = in ? v[((size_t)t * rows + c) * 32 + s] : 0.f;
-            const float a = seg_scan(w * x, ray, lane);
+            const float a = esr_wave_segscan_add(w * x, ray, lane);
             if (tail) atomicAdd(&out[3 * ray + c], a);
         }
     }
