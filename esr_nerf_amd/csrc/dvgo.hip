@@ -474,7 +474,8 @@ __global__ void __launch_bounds__(DVGO_BLOCK) dvgo_count_kernel(esr_dvgo_t P, es
     float *const dst[1] = {sum};
     const float one[1] = {1.f};
     for (int64_t r = (int64_t)blockIdx.x * DVGO_BLOCK + threadIdx.x; r < R.n_rays; r += (int64_t)gridDim.x * DVGO_BLOCK) {
-        const DvgoRay y = dvgo_ray(R, g, r);
+        DvgoRay y = dvgo_ray(R, g, r);
+        y.u = 0.f;        // the view count's samples are unjittered whatever rays->jitter holds (esr_hip.h)
         CellAcc<1> acc;
         acc_reset<1>(acc);
         for (int j = 0; j < S; ++j) {
