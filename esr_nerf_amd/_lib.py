@@ -7,15 +7,14 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 import torch
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libesr_hip.so")
+from .build import HEADER, LIB as LIB_PATH
 # developer experiments only (python -m esr_nerf_amd.build --variant builds alternative libraries; tools/ab_env.sh times them
 # side by side on one box)
 LIB_PATH = os.environ.get("ESR_LIB_PATH", LIB_PATH)
-ABI_VERSION = 43
 _lib = None
 
 
@@ -44,9 +43,6 @@ class EsrMarch(C.Structure):               # esr_march_t
                                           "rec_step", "rec_w", "rec_sdf", "dweight", "dlast", "grad_sdf", "grad_gg",
                                           "dsdf_rec")] + \
                [("accumulate", C.c_int32), ("cache", C.c_void_p)]
-
-
-MARCH_COARSE, MARCH_GRAD_ALPHA = 1, 2      # ESR_MARCH_COARSE, ESR_MARCH_GRAD_ALPHA
 
 
 class EsrFeatArgs(C.Structure):
@@ -134,16 +130,6 @@ class EsrCamera(C.Structure):           # esr_camera_t
     _fields_ = [(n, C.c_float) for n in ("fx", "fy", "cx", "cy")] + [(n, C.c_int32) for n in ("width", "height", "n_views")]
 
 
-CAMERA_LDS_VIEWS = 256                  # ESR_CAMERA_LDS_VIEWS
-CAMERA_BOUNDS_BLOCKS = 1024             # ESR_CAMERA_BOUNDS_BLOCKS
-RESAMPLE_MAX_C = 16                     # ESR_RESAMPLE_MAX_C
-DENSITY_BOUNDS_BLOCKS = 1024            # ESR_DENSITY_BOUNDS_BLOCKS
-PARTITION_BLOCK = 1024                  # ESR_PARTITION_BLOCK
-PARTITION_SCAN_TILE = 1024              # ESR_PARTITION_SCAN_TILE
-SIMPLIFY_MAX_C = 16                     # ESR_SIMPLIFY_MAX_C
-SIMPLIFY_DEBUG = 15                     # ESR_SIMPLIFY_DEBUG
-
-
 class EsrRegroupStats(C.Structure):     # esr_regroup_stats_t
     _fields_ = [(n, C.c_int64) for n in ("n_set", "n_clear", "n_nan")] + \
                [(n, C.c_float) for n in ("min_all", "max_all", "min_set", "max_set", "min_clear", "max_clear")]
@@ -160,122 +146,50 @@ class EsrWgradJob(C.Structure):
                 ("gw", C.c_void_p), ("gb", C.c_void_p), ("X16", C.c_void_p), ("amax", C.c_void_p)]
 
 
-# every exported symbol of include/esr_hip.h (checked by tests/test_host.py::test_library_loads_and_exports_every_header_symbol)
-EXPORTS = [
-    "esr_abi_version", "esr_build_info",
-    "esr_sample_count", "esr_sample_fill", "esr_alpha2weight_fwd", "esr_alpha2weight_bwd",
-    "esr_tv_add_grad", "esr_segment_sum",
-    "esr_sample_count_f64", "esr_sample_fill_f64", "esr_alpha2weight_fwd_f64", "esr_alpha2weight_bwd_f64",
-    "esr_infer_t_minmax", "esr_infer_n_samples", "esr_infer_ray_start_dir", "esr_sample_ndc_pts", "esr_sample_bg_pts",
-    "esr_maskcache_lookup", "esr_raw2alpha", "esr_raw2alpha_bwd", "esr_tv_add_grad_masked",
-    "esr_march_count", "esr_march_fill", "esr_march_bwd", "esr_fine_march_cache_floats",
-    "esr_fine_plan_begin", "esr_fine_plan", "esr_fine_plan_totals", "esr_fine_plan_offsets",
-    "esr_fine_feat_fwd", "esr_fine_feat_fwd_x16", "esr_fine_feat_x16_bytes", "esr_fine_feat_bwd",
-    "esr_mlp_packed_floats", "esr_mlp_pack", "esr_mlp_pack_batch", "esr_mlp_packed_split_elems", "esr_mlp_split_gain_offset", "esr_mlp_split_range_flag", "esr_mlp_fwd_split", "esr_mlp_fwd_fine_split", "esr_mlp_dgrad_split", "esr_mlp_dgrad_fine_split", "esr_absmax", "esr_mlp_fwd", "esr_mlp_fwd_mixed", "esr_mlp_fwd_fine", "esr_mlp_dgrad_fine", "esr_mlp_fwd_fine_bf16", "esr_mlp_dgrad_fine_bf16", "esr_mlp_dgrad", "esr_mlp_wgrad", "esr_mlp_wgrad_batch", "esr_tone_wgrad_scratch_floats", "esr_tone_wgrad_recompute", "esr_tone_wgrad_recompute_bf16", "esr_tone_wgrad_recompute_split",
-    "esr_mlp_wgrad_scratch_floats",
-    "esr_fine_tone_in_fwd", "esr_fine_composite_fwd", "esr_fine_composite_bwd",
-    "esr_fine_tone_in_bwd", "esr_fine_tone_dgrad_split", "esr_fine_loss_fwd_bwd_dp",
-    "esr_expgrad_fwd", "esr_expgrad_bwd", "esr_lts_dirs", "esr_lts_ref_order", "esr_lts_perturb", "esr_lts_gather_rows",
-    "esr_lts_gather_points", "esr_lts_combine_fwd", "esr_lts_combine_bwd",
-    "esr_act_fwd", "esr_act_bwd", "esr_act_batch", "esr_lts_gather_rows_batch", "esr_pair_loss_batch", "esr_lts_ref_order_inv", "esr_lts_dirs_rays", "esr_composite3_fwd", "esr_composite3_bwd", "esr_lts_tone_in_bwd",
-    "esr_sample_points", "esr_pair_loss_fwd_bwd", "esr_emit_edit",
-    "esr_gauss3d_fwd", "esr_gauss3d_bwd", "esr_central_grad_fwd", "esr_central_grad_bwd",
-    "esr_coarse_feat_fwd", "esr_coarse_feat_bwd", "esr_coarse_shade_fwd", "esr_coarse_shade_bwd",
-    "esr_adam_step", "esr_eval_aux", "esr_eval_disp",
-    "esr_mlp_packed_bf16_elems", "esr_mlp_pack_bf16", "esr_mlp_fwd_bf16", "esr_mlp_dgrad_bf16", "esr_mlp_wgrad_bf16",
-    "esr_brick_floats", "esr_brick_flags", "esr_brick_pack", "esr_brick_unpack", "esr_brick_list", "esr_brick_list_scratch_ints",
-    "esr_smooth_grad_tv_fwd", "esr_smooth_grad_tv_bwd", "esr_host_choice_noreplace", "esr_host_choice_start", "esr_host_choice_wait",
-    "esr_mesh_field", "esr_mesh_blocks", "esr_mesh_count", "esr_mesh_emit",
-    "esr_cd_sample_count", "esr_cd_sample_fill", "esr_cd_cell_keys", "esr_cd_hash_insert", "esr_cd_downsample_round",
-    "esr_cd_nn",
-    "esr_dvgo_fwd", "esr_dvgo_eval", "esr_dvgo_bwd", "esr_dvgo_count", "esr_dvgo_count_add",
-    "esr_ssim", "esr_view_post", "esr_sqerr_sum", "esr_gamma_curve", "esr_mask_iou",
-    "esr_mask_dilate", "esr_edit_label",
-    "esr_ray_filter",
-    "esr_adam_step_live", "esr_brick_live_from_moments",
-    "esr_camera_rays", "esr_camera_batch", "esr_camera_bounds", "esr_ray_filter_cameras",
-    "esr_grid_resample", "esr_maxpool3d", "esr_nonempty_mask", "esr_density_bounds",
-    "esr_cc_link", "esr_cc_flatten", "esr_cc_face_labels", "esr_cc_stats",
-    "esr_emit_decide", "esr_emit_decide_bits", "esr_flags_pack", "esr_flags_unpack", "esr_flag_scan_bits",
-    "esr_index_partition_bits", "esr_regroup_stats_merge",
-    "esr_conv_packed_floats", "esr_conv_pack", "esr_conv_relu", "esr_maxpool_nhwc", "esr_lpips_layer",
-    "esr_raster_faces", "esr_raster_resolve", "esr_source_masks",
-    "esr_simplify_cell_keys", "esr_simplify_pair_keys", "esr_simplify_clusters", "esr_simplify_face_keys", "esr_simplify_keep",
-    "esr_bvh_keys", "esr_bvh_tree", "esr_bvh_fit", "esr_bvh_cast",
-]
-
-# full ctypes signatures (argument conversion checked on every call) of the entries that declare them
-SIGNATURES = {
-    **{f"esr_march_{w}": (C.c_int, [C.POINTER(EsrMarch), C.c_void_p]) for w in ("count", "fill", "bwd")},
-    "esr_mask_dilate": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "esr_edit_label": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
-                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                 C.c_void_p, C.c_void_p]),
-    "esr_ray_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_int32,
-                                 C.c_void_p, C.c_void_p, C.c_void_p]),
-    "esr_adam_step_live": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                     C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_void_p,
-                                     C.c_void_p]),
-    "esr_brick_live_from_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "esr_camera_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_void_p]),
-    "esr_camera_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float,
-                                   C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                   C.c_void_p]),
-    "esr_camera_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "esr_ray_filter_cameras": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_int32,
-                                         C.c_void_p, C.c_void_p, C.c_void_p]),
-    "esr_grid_resample": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
-                                    C.c_int32, C.c_void_p]),
-    "esr_maxpool3d": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "esr_nonempty_mask": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_float, C.c_float,
-                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                    C.c_void_p, C.c_void_p, C.c_void_p]),
-    "esr_density_bounds": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_float, C.c_float,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "esr_cc_link": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
-    "esr_cc_flatten": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "esr_cc_face_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "esr_cc_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
-                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                               C.c_void_p]),
-    "esr_emit_decide": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "esr_emit_decide_bits": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
-    "esr_flags_pack": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "esr_flags_unpack": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "esr_flag_scan_bits": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "esr_index_partition_bits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "esr_regroup_stats_merge": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "esr_conv_packed_floats": (C.c_int64, [C.c_int32] * 4),
-    "esr_conv_pack": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "esr_conv_relu": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
-                                C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "esr_maxpool_nhwc": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                   C.c_void_p]),
-    "esr_lpips_layer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                  C.c_void_p]),
-    "esr_raster_faces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                   C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
-                                   C.c_void_p]),
-    "esr_raster_resolve": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "esr_source_masks": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32,
-                                   C.c_void_p, C.c_void_p, C.c_void_p]),
-    "esr_simplify_cell_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
-    "esr_simplify_pair_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "esr_simplify_clusters": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double,
-                                        C.c_double, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p]),
-    "esr_simplify_face_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "esr_simplify_keep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
-                                    C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "esr_bvh_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "esr_bvh_tree": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "esr_bvh_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "esr_bvh_cast": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                               C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+# The C ABI is declared once, in include/esr_hip.h: its integer #defines are this module's constants (ESR_ABI_VERSION ->
+# ABI_VERSION, ESR_PARTITION_BLOCK -> PARTITION_BLOCK, ...), and SIGNATURES -- entry -> (restype, argtypes), in header order --
+# is parsed from its prototypes, so ctypes converts and checks every argument of every call: a bare Python int reaches an
+# int64_t parameter whole, a bare float a float or double one.  EXPORTS lists the entries.  A new entry point is declared in
+# the header and defined in its .hip file; only a new struct needs a class above.
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double}
+_RESTYPES = {"int": C.c_int, "int64_t": C.c_int64, "const char *": C.c_char_p}
+# the pointers that stay typed (every other one is a c_void_p: call sites pass byref()s, pointer arrays and plain addresses)
+_TYPED_POINTERS = {
+    **{(f"esr_march_{w}", "a"): C.POINTER(EsrMarch) for w in ("count", "fill", "bwd")},
+    ("esr_nonempty_mask", "mask_box_host"): C.POINTER(C.c_float), ("esr_density_bounds", "box_host"): C.POINTER(C.c_float),
 }
+
+
+def _parse_header(path):
+    """(integer #defines without their ESR_ prefix, SIGNATURES) of the header; a prototype it cannot type is an error."""
+    with open(path) as f:
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", "", f.read(), flags=re.S)
+    defines = {n: int(v) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+ESR_(\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$", text, re.M)}
+    signatures, pointers = {}, set()
+    for res, name, params in re.findall(r"^[ \t]*(int|int64_t|const char \*)\s*(esr_\w+)\s*\(([^)]*)\)\s*;", text, re.M):
+        args = []
+        for param in (" ".join(p.split()) for p in params.split(",") if p.strip() != "void"):
+            m = re.fullmatch(r"(.*?)(\w+)", param)
+            ctype, pname = m.group(1).strip(), m.group(2)
+            if ctype.endswith("*"):
+                args.append(_TYPED_POINTERS.get((name, pname), C.c_void_p))
+                pointers.add((name, pname))
+            elif ctype in _SCALARS:
+                args.append(_SCALARS[ctype])
+            else:
+                raise RuntimeError(f"{path}: {name}: parameter `{param}` has a type the ctypes binding does not know")
+        signatures[name] = (_RESTYPES[res], args)
+    if set(_TYPED_POINTERS) - pointers:
+        raise RuntimeError(f"{path}: not pointer parameters of the header: {sorted(set(_TYPED_POINTERS) - pointers)}")
+    unparsed = set(re.findall(r"\b(esr_\w+)\s*\(", text)) - set(signatures)
+    if unparsed:
+        raise RuntimeError(f"{path}: prototypes the ctypes binding cannot read: {sorted(unparsed)}")
+    return defines, signatures
+
+
+_defines, SIGNATURES = _parse_header(HEADER)
+globals().update(_defines)
+EXPORTS = list(SIGNATURES)
 
 
 def lib() -> C.CDLL:
@@ -287,32 +201,8 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -m esr_nerf_amd.build` "
                 "(there is no CPU fallback for the HIP path)")
         L = C.CDLL(LIB_PATH)
-        L.esr_abi_version.restype = C.c_int
-        L.esr_build_info.restype = C.c_char_p
-        if hasattr(L, "esr_mlp_packed_floats"):
-            L.esr_mlp_packed_floats.restype = C.c_int64
-            L.esr_mlp_wgrad_scratch_floats.restype = C.c_int64
-            L.esr_tone_wgrad_scratch_floats.restype = C.c_int64
-            L.esr_fine_march_cache_floats.restype = C.c_int64
-        if hasattr(L, "esr_fine_feat_x16_bytes"):
-            L.esr_fine_feat_x16_bytes.restype = C.c_int64
-        if hasattr(L, "esr_brick_list_scratch_ints"):
-            L.esr_brick_list_scratch_ints.restype = C.c_int64
-        if hasattr(L, "esr_mlp_packed_bf16_elems"):
-            L.esr_mlp_packed_bf16_elems.restype = C.c_int64
-        if hasattr(L, "esr_mlp_packed_split_elems"):
-            L.esr_mlp_packed_split_elems.restype = C.c_int64
-        if hasattr(L, "esr_mlp_split_gain_offset"):
-            L.esr_mlp_split_gain_offset.restype = C.c_int64
-        if hasattr(L, "esr_mesh_blocks"):
-            L.esr_mesh_blocks.restype = C.c_int64
-        for name in ("esr_cd_sample_count", "esr_cd_sample_fill", "esr_cd_cell_keys", "esr_cd_hash_insert",
-                     "esr_cd_downsample_round", "esr_cd_nn", "esr_ssim", "esr_view_post", "esr_sqerr_sum", "esr_gamma_curve",
-                     "esr_mask_iou"):
-            if hasattr(L, name):
-                getattr(L, name).restype = C.c_int
         for name, (res, args) in SIGNATURES.items():
-            if hasattr(L, name):
+            if hasattr(L, name):               # (a variant library may lack an entry)
                 getattr(L, name).restype, getattr(L, name).argtypes = res, args
         if L.esr_abi_version() != ABI_VERSION:
             raise RuntimeError("libesr_hip.so ABI version mismatch: rebuild")

@@ -130,14 +130,14 @@ def sample_mesh_points(vertices, triangles, thresh: float = 0.2, device=None) ->
     with torch.cuda.device(dev):
         s = _lib.stream_ptr(dev)
         counts = torch.empty(n_tri, dtype=torch.int64, device=dev)
-        _lib.check(L.esr_cd_sample_count(_lib.ptr(v), _lib.ptr(f), n_tri, C.c_double(thresh), _lib.ptr(counts), s),
+        _lib.check(L.esr_cd_sample_count(_lib.ptr(v), _lib.ptr(f), n_tri, thresh, _lib.ptr(counts), s),
                    "esr_cd_sample_count")
         incl = torch.cumsum(counts, 0)
         total = int(incl[-1]) if n_tri else 0
         out = torch.empty(v.shape[0] + total, 3, dtype=torch.float64, device=dev)
         out[:v.shape[0]] = v
         if total:
-            _lib.check(L.esr_cd_sample_fill(_lib.ptr(v), _lib.ptr(f), n_tri, C.c_double(thresh), _lib.ptr(incl - counts),
+            _lib.check(L.esr_cd_sample_fill(_lib.ptr(v), _lib.ptr(f), n_tri, thresh, _lib.ptr(incl - counts),
                                             _lib.ptr(out[v.shape[0]:]), s), "esr_cd_sample_fill")
     return out
 
@@ -166,7 +166,7 @@ def radius_downsample(points, thresh: float, order=None, return_rounds: bool = F
             while True:
                 flags.zero_()
                 for r in range(_ROUNDS_PER_READ):
-                    _lib.check(L.esr_cd_downsample_round(C.byref(index.ix), _lib.ptr(p), n, C.c_double(thresh),
+                    _lib.check(L.esr_cd_downsample_round(C.byref(index.ix), _lib.ptr(p), n, thresh,
                                                          _lib.ptr(state), _lib.ptr(flags[r:r + 1]), s),
                                "esr_cd_downsample_round")
                 f = flags.cpu().tolist()
@@ -205,7 +205,7 @@ def nn_distance(queries, targets, max_dist: float = 20.0, cell: float | None = N
     h = max(cell if cell is not None else _nn_cell(t), max_dist / _NN_MIN_CELLS)
     index = CellIndex(t, h, coarse=_COARSE)
     with torch.cuda.device(dev):
-        _lib.check(L.esr_cd_nn(C.byref(index.ix), _lib.ptr(q), q.shape[0], C.c_double(max_dist), _lib.ptr(out),
+        _lib.check(L.esr_cd_nn(C.byref(index.ix), _lib.ptr(q), q.shape[0], max_dist, _lib.ptr(out),
                                _lib.stream_ptr(dev)), "esr_cd_nn")
     return out
 

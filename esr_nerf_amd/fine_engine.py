@@ -592,7 +592,7 @@ class FineEngine:
             L.esr_tone_wgrad_recompute_bf16 if self.bf16 else L.esr_tone_wgrad_recompute
         self._run(name, fn, _lib.ptr(x), _lib.ptr(dz), _lib.ptr(w0.detach()), _lib.ptr(b0.detach()), _lib.ptr(w1.detach()),
                   *((_lib.ptr(amax),) if amax is not None else ()), t0, t1, _lib.ptr(gw[0]), _lib.ptr(gb[0]), _lib.ptr(gw[1]),
-                  _lib.ptr(gb[1]), _lib.ptr(self.tone_scratch), C.c_int64(self.tone_scratch.numel()), s)
+                  _lib.ptr(gb[1]), _lib.ptr(self.tone_scratch), self.tone_scratch.numel(), s)
 
     # -- forward -----------------------------------------------------------------
     def forward(self, scene, rays_o, rays_d, viewdirs, em_modes, mask_density, sdf, off_color, emo_color, prelude=None,
@@ -737,13 +737,13 @@ class FineEngine:
             aux = torch.empty(T * 8 * 32, dtype=torch.float32, device=dev)
             rt = (C.c_float * 9)(*[float(v) for v in pos_rt.detach().cpu().reshape(-1).tolist()])
             self._run("eval_aux", L.esr_eval_aux, _lib.ptr(X), x_rows, *cols, _lib.ptr(rec[0]), _lib.ptr(rec[1]), T, rt,
-                      C.c_float(scene.stepdist), _lib.ptr(aux), s)
+                      scene.stepdist, _lib.ptr(aux), s)
             for name, row0, dst in (("normal", 0, normal), ("depth", 4, depth3)):       # aux rows 0-2: normal colour | row 4: depth
                 self._run(f"composite3_fwd({name})", L.esr_composite3_fwd, C.c_void_p(aux.data_ptr() + row0 * 32 * 4), 8,
                           _lib.ptr(rec[0]), _lib.ptr(rec[2]), T, _lib.ptr(dst), s)
             if between is not None:
                 between()
-        self._run("eval_disp", L.esr_eval_disp, _lib.ptr(depth3), _lib.ptr(bg), C.c_float(far), n, _lib.ptr(depth), _lib.ptr(disp), s)
+        self._run("eval_disp", L.esr_eval_disp, _lib.ptr(depth3), _lib.ptr(bg), far, n, _lib.ptr(depth), _lib.ptr(disp), s)
         return normal, depth, disp
 
     # -- backward ----------------------------------------------------------------
@@ -816,7 +816,7 @@ class FineEngine:
                 if split:                               # (non-NULL amax selects the split-fp16 weight-gradient kernel)
                     jb.amax = ctx.amax.data_ptr()
             self._run("mlp_wgrad(all)", L.esr_mlp_wgrad_batch, jobs, len(todo), 1 if self.bf16 else 0,
-                      _lib.ptr(self.wgrad_scratch), C.c_int64(self.wgrad_scratch.numel()), s_)
+                      _lib.ptr(self.wgrad_scratch), self.wgrad_scratch.numel(), s_)
 
         if ta == 0:
             march_bwd(s)
@@ -909,6 +909,6 @@ class FineEngine:
         g_last = torch.empty_like(last)
         self._run("loss", self.L.esr_fine_loss_fwd_bwd_dp,
                   _lib.ptr(srgb), _lib.ptr(lin), _lib.ptr(last), _lib.ptr(rgbs.contiguous()), n,
-                  C.c_float(1.0 if white_bg else 0.0), C.c_float(weight_linear), C.c_float(weight_entropy_last),
-                  C.c_float(scale), _lib.ptr(loss), _lib.ptr(g_srgb), _lib.ptr(g_lin), _lib.ptr(g_last), self._s())
+                  1.0 if white_bg else 0.0, weight_linear, weight_entropy_last,
+                  scale, _lib.ptr(loss), _lib.ptr(g_srgb), _lib.ptr(g_lin), _lib.ptr(g_last), self._s())
         return loss, g_last, g_srgb, g_lin

@@ -31,7 +31,6 @@ through ``ops=`` to rehearse the protocols on CPU.
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import List, Optional, Tuple
 
 import torch
@@ -48,12 +47,12 @@ class HipBrickOps:
         self.brick = int(self.L.esr_brick_floats())
 
     def flags(self, flat: torch.Tensor, out: torch.Tensor):
-        _lib.check(self.L.esr_brick_flags(_lib.ptr(flat), C.c_int64(flat.numel()), _lib.ptr(out),
+        _lib.check(self.L.esr_brick_flags(_lib.ptr(flat), flat.numel(), _lib.ptr(out),
                                           _lib.stream_ptr(flat.device)), "esr_brick_flags")
 
     def pack(self, flat: torch.Tensor, idx: torch.Tensor, packed: torch.Tensor):
-        _lib.check(self.L.esr_brick_pack(_lib.ptr(flat), C.c_int64(flat.numel()), _lib.ptr(idx),
-                                         C.c_int64(idx.numel()), _lib.ptr(packed),
+        _lib.check(self.L.esr_brick_pack(_lib.ptr(flat), flat.numel(), _lib.ptr(idx),
+                                         idx.numel(), _lib.ptr(packed),
                                          _lib.stream_ptr(flat.device)), "esr_brick_pack")
 
     def list(self, flags: torch.Tensor, cap: int):
@@ -64,13 +63,13 @@ class HipBrickOps:
             self._scratch = torch.empty(int(self.L.esr_brick_list_scratch_ints()), dtype=torch.int32, device=dev)
         idx = torch.empty(cap, dtype=torch.int64, device=dev)
         count = torch.empty(1, dtype=torch.int64, device=dev)
-        _lib.check(self.L.esr_brick_list(_lib.ptr(flags), C.c_int64(flags.numel()), C.c_int64(cap), _lib.ptr(idx),
+        _lib.check(self.L.esr_brick_list(_lib.ptr(flags), flags.numel(), cap, _lib.ptr(idx),
                                          _lib.ptr(count), _lib.ptr(self._scratch), _lib.stream_ptr(dev)), "esr_brick_list")
         return idx, count
 
     def unpack(self, packed: torch.Tensor, idx: torch.Tensor, flat: torch.Tensor):
-        _lib.check(self.L.esr_brick_unpack(_lib.ptr(packed), _lib.ptr(idx), C.c_int64(idx.numel()),
-                                           _lib.ptr(flat), C.c_int64(flat.numel()),
+        _lib.check(self.L.esr_brick_unpack(_lib.ptr(packed), _lib.ptr(idx), idx.numel(),
+                                           _lib.ptr(flat), flat.numel(),
                                            _lib.stream_ptr(flat.device)), "esr_brick_unpack")
 
 

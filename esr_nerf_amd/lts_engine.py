@@ -150,7 +150,7 @@ class _PointDraw:
         self._lock = bg.lock
         self._lock.acquire()
         try:
-            _lib.check(_lib.lib().esr_host_choice_start(C.c_void_p(key_addr), C.c_void_p(pos_addr), C.c_int64(n), C.c_int64(k),
+            _lib.check(_lib.lib().esr_host_choice_start(C.c_void_p(key_addr), C.c_void_p(pos_addr), n, k,
                                                         C.c_void_p(self._out_t.data_ptr()), C.byref(self._job)), "esr_host_choice_start")
         except Exception:
             self._job = None
@@ -379,7 +379,7 @@ class LtsEngine(FineEngine):
             else:
                 self._run(f"mlp_wgrad({net})[{P.name}]", self.mlp_wgrad, kind, _lib.ptr(x), crow,
                           _lib.ptr_array(H), _lib.ptr_array(dZ), _lib.ptr(dz), t0, t1, _lib.ptr_array(gw),
-                          _lib.ptr_array(gb), _lib.ptr(self.wgrad_scratch), C.c_int64(self.wgrad_scratch.numel()), self._s())
+                          _lib.ptr_array(gb), _lib.ptr(self.wgrad_scratch), self.wgrad_scratch.numel(), self._s())
         return dX
 
     def _act(self, P, zname, out, rows, n_ch, act, bwd_g=None, tiles=None):
@@ -549,7 +549,7 @@ class LtsEngine(FineEngine):
             perm, rec_ray = self._ref_order(P0, cnt3, off3)
             eg = torch.empty(T * 32, 4, device=dev)
             self._run("expgrad_fwd", L.esr_expgrad_fwd, sp, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(P0.bufs["rec_ray"]),
-                      _lib.ptr(P0.bufs["rec_step"]), None, None, C.c_float(0.0), _lib.ptr(sdf), T * 32, 0, _lib.ptr(eg), s)
+                      _lib.ptr(P0.bufs["rec_step"]), None, None, 0.0, _lib.ptr(sdf), T * 32, 0, _lib.ptr(eg), s)
             pts_all = torch.empty(T * 32, 3, device=dev)
             self._run("sample_points", L.esr_sample_points, sp, _lib.ptr(rays_o), _lib.ptr(rays_d),
                       _lib.ptr(P0.bufs["rec_ray"]), _lib.ptr(P0.bufs["rec_step"]), T * 32, _lib.ptr(pts_all), s)
@@ -670,7 +670,7 @@ class LtsEngine(FineEngine):
             eg = torch.empty(m, 4, device=dev)
             sv = torch.empty(m, 4, device=dev)
             for zero_pad, o in ((0, eg), (1, sv)):
-                self._run("expgrad_fwd(pts)", L.esr_expgrad_fwd, sp, None, None, None, None, _lib.ptr(p), None, C.c_float(0.0),
+                self._run("expgrad_fwd(pts)", L.esr_expgrad_fwd, sp, None, None, None, None, _lib.ptr(p), None, 0.0,
                           _lib.ptr(sdf), m, zero_pad, _lib.ptr(o), self._s())
             sdf_p = sv[:, 0].contiguous()
             vd = torch.zeros(m, 3, device=dev)             # view directions are no input of these two nets
@@ -725,7 +725,7 @@ class LtsEngine(FineEngine):
         sp = C.byref(scene)
         eg = torch.empty(T * 32, 4, device=dev)
         self._run("expgrad_fwd", L.esr_expgrad_fwd, sp, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(P0.bufs["rec_ray"]),
-                  _lib.ptr(P0.bufs["rec_step"]), None, None, C.c_float(0.0), _lib.ptr(sdf), T * 32, 0, _lib.ptr(eg), s)
+                  _lib.ptr(P0.bufs["rec_step"]), None, None, 0.0, _lib.ptr(sdf), T * 32, 0, _lib.ptr(eg), s)
         pts_all = torch.empty(T * 32, 3, device=dev)
         self._run("sample_points", L.esr_sample_points, sp, _lib.ptr(rays_o), _lib.ptr(rays_d),
                   _lib.ptr(P0.bufs["rec_ray"]), _lib.ptr(P0.bufs["rec_step"]), T * 32, _lib.ptr(pts_all), s)
@@ -843,7 +843,7 @@ class LtsEngine(FineEngine):
         # exact normals (+ positions) of every surviving sample
         eg = torch.empty(T * 32, 4, device=dev)
         self._run("expgrad_fwd", L.esr_expgrad_fwd, sp, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(P0.bufs["rec_ray"]),
-                  _lib.ptr(P0.bufs["rec_step"]), None, None, C.c_float(0.0), _lib.ptr(sdf), T * 32, 0, _lib.ptr(eg), s)
+                  _lib.ptr(P0.bufs["rec_step"]), None, None, 0.0, _lib.ptr(sdf), T * 32, 0, _lib.ptr(eg), s)
         pts_all = torch.empty(T * 32, 3, device=dev)
         self._run("sample_points", L.esr_sample_points, sp, _lib.ptr(rays_o), _lib.ptr(rays_d),
                   _lib.ptr(P0.bufs["rec_ray"]), _lib.ptr(P0.bufs["rec_step"]), T * 32, _lib.ptr(pts_all), s)
@@ -883,11 +883,11 @@ class LtsEngine(FineEngine):
         pts_e = torch.empty(m3, 3, device=dev)
         nn_, ne_ = nn_.contiguous(), ne_.contiguous()
         self._run("lts_perturb", L.esr_lts_perturb, _lib.ptr(pts_all), _lib.ptr(perm), _lib.ptr(nn_), _lib.ptr(ne_),
-                  C.c_float(ctx.eps["emit"]), m3, _lib.ptr(noise_n), _lib.ptr(pts_e), s)
+                  ctx.eps["emit"], m3, _lib.ptr(noise_n), _lib.ptr(pts_e), s)
         P0.keep += [nn_, ne_]
         eg_eps = torch.empty(T * 32, 4, device=dev)
         self._run("expgrad_fwd(eps)", L.esr_expgrad_fwd, sp, _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(P0.bufs["rec_ray"]),
-                  _lib.ptr(P0.bufs["rec_step"]), None, _lib.ptr(noise_n), C.c_float(ctx.eps["normal"]), _lib.ptr(sdf),
+                  _lib.ptr(P0.bufs["rec_step"]), None, _lib.ptr(noise_n), ctx.eps["normal"], _lib.ptr(sdf),
                   T * 32, 0, _lib.ptr(eg_eps), s)
         ctx.t.update(noise_n=noise_n)
         # emit_eps / brdf_eps: forward only (explicit points in reference order)
@@ -899,7 +899,7 @@ class LtsEngine(FineEngine):
         eps_out = {}
 
         def eps_pass():
-            self._run("expgrad_fwd(pts)", L.esr_expgrad_fwd, sp, None, None, None, None, _lib.ptr(pts_e), None, C.c_float(0.0),
+            self._run("expgrad_fwd(pts)", L.esr_expgrad_fwd, sp, None, None, None, None, _lib.ptr(pts_e), None, 0.0,
                       _lib.ptr(sdf), m3, 1, _lib.ptr(sv), self._s())
             sdf_e.copy_(sv[:, 0])
             self._feat_args_points(P3, pts_e, vd_e, sdf_e, sdf, (None, emog, brdfg))
@@ -1121,7 +1121,7 @@ class LtsEngine(FineEngine):
             dz.record_stream(torch.cuda.current_stream(self.device))      # may be a transient allocation of the main stream
         if jobs:
             self._run("mlp_wgrad(all)", self.L.esr_mlp_wgrad_batch, arr, len(jobs), 1 if self.bf16 else 0,
-                      _lib.ptr(self.wgrad_scratch), C.c_int64(self.wgrad_scratch.numel()), self._s())
+                      _lib.ptr(self.wgrad_scratch), self.wgrad_scratch.numel(), self._s())
         for fn, dz in self._wgrad_extra:
             dz.record_stream(torch.cuda.current_stream(self.device))
             fn()
@@ -1246,7 +1246,7 @@ class LtsEngine(FineEngine):
             g4 = self._z(T * 32, 4, device=dev)
             g4[perm, 1:4] = g[key]
             self._run("expgrad_bwd", L.esr_expgrad_bwd, sp, _lib.ptr(b["rays_o"]), _lib.ptr(b["rays_d"]),
-                      _lib.ptr(P0.bufs["rec_ray"]), _lib.ptr(P0.bufs["rec_step"]), None, _lib.ptr(noise), C.c_float(eps),
+                      _lib.ptr(P0.bufs["rec_ray"]), _lib.ptr(P0.bufs["rec_step"]), None, _lib.ptr(noise), eps,
                       _lib.ptr(g4), T * 32, 0, _lib.ptr(grads["sdf"]), s)
 
         # ---- perturbed material heads ("etc/emit_eps": PDRA's emission-smoothness loss, pdra.py:455-457)

@@ -96,14 +96,13 @@ def marching_cubes(u: torch.Tensor, threshold: float = 0.0):
     u = u.contiguous()
     dims = [int(v) for v in u.shape]
     dev = u.device
-    thr = C.c_float(threshold)
     nb = int(L.esr_mesh_blocks(*dims))
     if nb < 0:
         raise ValueError(f"marching_cubes: every lattice dimension must be in [2, 1024], got {dims}")
     with torch.cuda.device(dev):
         s = _lib.stream_ptr(dev)
         counts = torch.empty(2 * nb, dtype=torch.int64, device=dev)
-        _lib.check(L.esr_mesh_count(_lib.ptr(u), *dims, thr, _lib.ptr(counts), s), "esr_mesh_count")
+        _lib.check(L.esr_mesh_count(_lib.ptr(u), *dims, threshold, _lib.ptr(counts), s), "esr_mesh_count")
         offsets, n_v, n_f = _scan(counts, nb)
         verts = torch.empty(n_v, 3, dtype=torch.float64, device=dev)
         tris = torch.empty(n_f, 3, dtype=torch.int64, device=dev)
@@ -112,7 +111,7 @@ def marching_cubes(u: torch.Tensor, threshold: float = 0.0):
         if n_v >= 2 ** 31:
             raise RuntimeError(f"marching_cubes: {n_v} vertices exceed the kernels' 31-bit vertex ids")
         vid = torch.empty(dims, dtype=torch.int32, device=dev)
-        _lib.check(L.esr_mesh_emit(_lib.ptr(u), *dims, thr, _lib.ptr(offsets), _lib.ptr(vid), _lib.ptr(verts),
+        _lib.check(L.esr_mesh_emit(_lib.ptr(u), *dims, threshold, _lib.ptr(offsets), _lib.ptr(vid), _lib.ptr(verts),
                                    _lib.ptr(tris), s), "esr_mesh_emit")
     return verts, tris
 

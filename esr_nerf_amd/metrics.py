@@ -74,7 +74,7 @@ def rgb_ssim(img0, img1, max_val, filter_size=11, filter_sigma=1.5, k1=0.01, k2=
         ssim_map = torch.empty(H - filter_size + 1, W - filter_size + 1, 3, dtype=torch.float64, device=dev) if return_map else None
         scratch = torch.empty(_BLOCKS + 1, dtype=torch.float64, device=dev)
         _lib.check(_lib.lib().esr_ssim(_lib.ptr(a), _lib.ptr(b), H, W, taps.ctypes.data_as(C.c_void_p), filter_size,
-                                       C.c_double(c1), C.c_double(c2), _lib.ptr(ssim_map), _lib.ptr(scratch),
+                                       c1, c2, _lib.ptr(ssim_map), _lib.ptr(scratch),
                                        C.c_void_p(scratch.data_ptr() + 8 * _BLOCKS), _lib.stream_ptr(dev)), "esr_ssim")
         return ssim_map if return_map else float(scratch[_BLOCKS])
 
@@ -124,7 +124,7 @@ def IoU(mask1, mask2):
     dev = _same_device(m1, m2)
     with torch.cuda.device(dev):
         counts = torch.empty(2, dtype=torch.int64, device=dev)
-        _lib.check(_lib.lib().esr_mask_iou(_lib.ptr(m1), _lib.ptr(m2), C.c_int64(m1.numel()), _lib.ptr(counts), _lib.stream_ptr(dev)),
+        _lib.check(_lib.lib().esr_mask_iou(_lib.ptr(m1), _lib.ptr(m2), m1.numel(), _lib.ptr(counts), _lib.stream_ptr(dev)),
                    "esr_mask_iou")
         inter, union = counts.tolist()
     union = max(1, union)
@@ -145,7 +145,7 @@ def apply_gamma_curve(image):
     x = _on_device(image, torch.float32)
     y = torch.empty_like(x)
     with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().esr_gamma_curve(_lib.ptr(x), C.c_int64(x.numel()), _lib.ptr(y), _lib.stream_ptr(x.device)), "esr_gamma_curve")
+        _lib.check(_lib.lib().esr_gamma_curve(_lib.ptr(x), x.numel(), _lib.ptr(y), _lib.stream_ptr(x.device)), "esr_gamma_curve")
     return y
 
 
@@ -158,7 +158,7 @@ def sqerr_sum(a, b) -> torch.Tensor:
     dev = _same_device(a, b)
     with torch.cuda.device(dev):
         scratch = torch.empty(_BLOCKS + 1, dtype=torch.float64, device=dev)
-        _lib.check(_lib.lib().esr_sqerr_sum(_lib.ptr(a), _lib.ptr(b), C.c_int64(a.numel()), _lib.ptr(scratch),
+        _lib.check(_lib.lib().esr_sqerr_sum(_lib.ptr(a), _lib.ptr(b), a.numel(), _lib.ptr(scratch),
                                             C.c_void_p(scratch.data_ptr() + 8 * _BLOCKS), _lib.stream_ptr(dev)), "esr_sqerr_sum")
     return scratch[_BLOCKS:]
 

@@ -20,7 +20,6 @@ out as the multiplicative step-to-step factor the trainers apply to every group'
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import os
 
@@ -257,16 +256,16 @@ class Adam(torch.optim.Optimizer):
                 self._live.pop(id(p), None)             # (a dense step moves moments the flags know nothing about)
                 rc = L.esr_adam_step(_lib.ptr(pf), _lib.ptr(gf), _lib.ptr(mf), _lib.ptr(vf),
                                      _lib.ptr(_flat_storage(plr)) if plr is not None else None,
-                                     C.c_int64(pf.numel()), C.c_float(group["lr"]), C.c_float(beta1), C.c_float(beta2),
-                                     C.c_float(group["eps"]), C.c_float(group["weight_decay"]), int(st["step"]),
+                                     pf.numel(), group["lr"], beta1, beta2,
+                                     group["eps"], group["weight_decay"], int(st["step"]),
                                      _lib.stream_ptr(p.device))
                 _lib.check(rc, "esr_adam_step")
         return loss
 
 
 def _hip_adam(p, g, m, v, lr, beta1, beta2, eps, step):
-    rc = _lib.lib().esr_adam_step(_lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), None, C.c_int64(p.numel()),
-                                  C.c_float(lr), C.c_float(beta1), C.c_float(beta2), C.c_float(eps), C.c_float(0.0),
+    rc = _lib.lib().esr_adam_step(_lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), None, p.numel(),
+                                  lr, beta1, beta2, eps, 0.0,
                                   int(step), _lib.stream_ptr(p.device))
     _lib.check(rc, "esr_adam_step")
 

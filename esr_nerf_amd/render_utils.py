@@ -9,7 +9,6 @@ RuntimeError like the reference's TORCH_CHECK(is_cuda / is_contiguous).
 """
 from __future__ import annotations
 
-import ctypes as C
 
 import torch
 
@@ -53,7 +52,7 @@ def sample_pts_on_rays(rays_o, rays_d, xyz_min, xyz_max, near, far, stepdist):
     s = _lib.stream_ptr(dev)
     _lib.check(count(
         _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(xyz_min), _lib.ptr(xyz_max),
-        C.c_float(float(near)), C.c_float(float(far)), C.c_float(float(stepdist)), C.c_int64(n),
+        float(near), float(far), float(stepdist), n,
         _lib.ptr(t_min), _lib.ptr(t_max), _lib.ptr(n_steps), _lib.ptr(cumsum), _lib.ptr(total), s),
         "esr_sample_count")
     m = int(total.item())          # same device->host sync as the reference (kernel.cu:212)
@@ -63,7 +62,7 @@ def sample_pts_on_rays(rays_o, rays_d, xyz_min, xyz_max, near, far, stepdist):
     step_id = torch.empty(m, dtype=_i64, device=dev)
     _lib.check(fill(
         _lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(xyz_min), _lib.ptr(xyz_max), _lib.ptr(t_min),
-        _lib.ptr(cumsum), C.c_float(float(stepdist)), C.c_int64(n), C.c_int64(m),
+        _lib.ptr(cumsum), float(stepdist), n, m,
         _lib.ptr(ray_pts), _lib.ptr(mask), _lib.ptr(ray_id), _lib.ptr(step_id), s),
         "esr_sample_fill")
     return [ray_pts, mask, ray_id, step_id, n_steps, t_min, t_max]
@@ -83,7 +82,7 @@ def alpha2weight(alpha, ray_id, n_rays):
     i_s = torch.empty(n_rays, dtype=_i64, device=dev)
     i_e = torch.empty(n_rays, dtype=_i64, device=dev)
     _lib.check((L.esr_alpha2weight_fwd if ft == _f32 else L.esr_alpha2weight_fwd_f64)(
-        _lib.ptr(alpha), _lib.ptr(ray_id), C.c_int64(m), C.c_int64(n_rays), _lib.ptr(weight),
+        _lib.ptr(alpha), _lib.ptr(ray_id), m, n_rays, _lib.ptr(weight),
         _lib.ptr(T), _lib.ptr(last), _lib.ptr(i_s), _lib.ptr(i_e), _lib.stream_ptr(dev)),
         "esr_alpha2weight_fwd")
     return [weight, T, last, i_s, i_e]
@@ -99,7 +98,7 @@ def alpha2weight_backward(alpha, weight, T, alphainv_last, i_start, i_end, n_ray
     grad = torch.empty_like(alpha)
     _lib.check((L.esr_alpha2weight_bwd if ft == _f32 else L.esr_alpha2weight_bwd_f64)(
         _lib.ptr(alpha), _lib.ptr(weight), _lib.ptr(T), _lib.ptr(alphainv_last), _lib.ptr(i_start),
-        _lib.ptr(i_end), C.c_int64(alpha.shape[0]), C.c_int64(int(n_rays)), _lib.ptr(grad_weights),
+        _lib.ptr(i_end), alpha.shape[0], int(n_rays), _lib.ptr(grad_weights),
         _lib.ptr(grad_last), _lib.ptr(grad), _lib.stream_ptr(alpha.device)),
         "esr_alpha2weight_bwd")
     return grad
@@ -111,9 +110,8 @@ def total_variation_add_grad(param, grad, wx, wy, wz, dense_mode):
     _chk(grad, "grad", _f32)
     L = _lib.lib()
     _lib.check(L.esr_tv_add_grad(
-        _lib.ptr(param), _lib.ptr(grad), C.c_float(float(wx)), C.c_float(float(wy)),
-        C.c_float(float(wz)), C.c_int64(param.shape[2]), C.c_int64(param.shape[3]),
-        C.c_int64(param.shape[4]), C.c_int64(param.numel()), C.c_int(1 if dense_mode else 0),
+        _lib.ptr(param), _lib.ptr(grad), float(wx), float(wy), float(wz),
+        param.shape[2], param.shape[3], param.shape[4], param.numel(), 1 if dense_mode else 0,
         _lib.stream_ptr(param.device)), "esr_tv_add_grad")
 
 
@@ -129,8 +127,8 @@ def segment_coo(src, index, out=None, dim_size=None, reduce="sum"):
     _chk(out, "out", _f32)
     c = 1 if src.dim() == 1 else src.shape[1]
     _lib.check(_lib.lib().esr_segment_sum(
-        _lib.ptr(src), _lib.ptr(index), C.c_int64(src.shape[0]), C.c_int64(c), _lib.ptr(out),
-        C.c_int64(out.shape[0]), _lib.stream_ptr(src.device)), "esr_segment_sum")
+        _lib.ptr(src), _lib.ptr(index), src.shape[0], c, _lib.ptr(out),
+        out.shape[0], _lib.stream_ptr(src.device)), "esr_segment_sum")
     return out
 
 
@@ -146,7 +144,7 @@ def infer_t_minmax(rays_o, rays_d, xyz_min, xyz_max, near, far):
     n = rays_o.shape[0]
     t_min, t_max = torch.empty(n, dtype=_f32, device=rays_o.device), torch.empty(n, dtype=_f32, device=rays_o.device)
     _lib.check(_lib.lib().esr_infer_t_minmax(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(xyz_min), _lib.ptr(xyz_max),
-                                             C.c_float(float(near)), C.c_float(float(far)), C.c_int64(n), _lib.ptr(t_min),
+                                             float(near), float(far), n, _lib.ptr(t_min),
                                              _lib.ptr(t_max), _lib.stream_ptr(rays_o.device)), "esr_infer_t_minmax")
     return [t_min, t_max]
 
@@ -156,8 +154,8 @@ def infer_n_samples(rays_d, t_min, t_max, stepdist):
         _chk(t, n, _f32)
     n = t_min.shape[0]
     out = torch.empty(n, dtype=_i64, device=t_min.device)
-    _lib.check(_lib.lib().esr_infer_n_samples(_lib.ptr(rays_d), _lib.ptr(t_min), _lib.ptr(t_max), C.c_float(float(stepdist)),
-                                              C.c_int64(n), _lib.ptr(out), _lib.stream_ptr(t_min.device)), "esr_infer_n_samples")
+    _lib.check(_lib.lib().esr_infer_n_samples(_lib.ptr(rays_d), _lib.ptr(t_min), _lib.ptr(t_max), float(stepdist),
+                                              n, _lib.ptr(out), _lib.stream_ptr(t_min.device)), "esr_infer_n_samples")
     return out
 
 
@@ -166,7 +164,7 @@ def infer_ray_start_dir(rays_o, rays_d, t_min):
     for t, n in ((rays_o, "rays_o"), (rays_d, "rays_d"), (t_min, "t_min")):
         _chk(t, n, _f32)
     start, dirs = torch.empty_like(rays_o), torch.empty_like(rays_o)
-    _lib.check(_lib.lib().esr_infer_ray_start_dir(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_min), C.c_int64(rays_o.shape[0]),
+    _lib.check(_lib.lib().esr_infer_ray_start_dir(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_min), rays_o.shape[0],
                                                   _lib.ptr(start), _lib.ptr(dirs), _lib.stream_ptr(rays_o.device)),
                "esr_infer_ray_start_dir")
     return [start, dirs]
@@ -180,7 +178,7 @@ def sample_ndc_pts_on_rays(rays_o, rays_d, xyz_min, xyz_max, N_samples):
     pts = torch.empty(n, S, 3, dtype=_f32, device=rays_o.device)
     mask = torch.empty(n, S, dtype=torch.bool, device=rays_o.device)
     _lib.check(_lib.lib().esr_sample_ndc_pts(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(xyz_min), _lib.ptr(xyz_max),
-                                             C.c_int32(S), C.c_int64(n), _lib.ptr(pts), _lib.ptr(mask),
+                                             S, n, _lib.ptr(pts), _lib.ptr(mask),
                                              _lib.stream_ptr(rays_o.device)), "esr_sample_ndc_pts")
     return [pts, mask]
 
@@ -190,8 +188,8 @@ def sample_bg_pts_on_rays(rays_o, rays_d, t_max, bg_preserve, N_samples):
         _chk(t, n, _f32)
     n, S = rays_o.shape[0], int(N_samples)
     pts = torch.empty(n, S, 3, dtype=_f32, device=rays_o.device)
-    _lib.check(_lib.lib().esr_sample_bg_pts(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_max), C.c_float(float(bg_preserve)),
-                                            C.c_int32(S), C.c_int64(n), _lib.ptr(pts), _lib.stream_ptr(rays_o.device)),
+    _lib.check(_lib.lib().esr_sample_bg_pts(_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(t_max), float(bg_preserve),
+                                            S, n, _lib.ptr(pts), _lib.stream_ptr(rays_o.device)),
                "esr_sample_bg_pts")
     return pts
 
@@ -203,8 +201,8 @@ def maskcache_lookup(world, xyz, xyz2ijk_scale, xyz2ijk_shift):
         _chk(t, n, _f32)
     out = torch.zeros(xyz.shape[0], dtype=torch.bool, device=xyz.device)
     _lib.check(_lib.lib().esr_maskcache_lookup(_lib.ptr(world), _lib.ptr(xyz), _lib.ptr(xyz2ijk_scale), _lib.ptr(xyz2ijk_shift),
-                                               C.c_int32(world.shape[0]), C.c_int32(world.shape[1]), C.c_int32(world.shape[2]),
-                                               C.c_int64(xyz.shape[0]), _lib.ptr(out), _lib.stream_ptr(xyz.device)),
+                                               world.shape[0], world.shape[1], world.shape[2],
+                                               xyz.shape[0], _lib.ptr(out), _lib.stream_ptr(xyz.device)),
                "esr_maskcache_lookup")
     return out
 
@@ -214,8 +212,8 @@ def _raw2alpha(density, shift, interval, per_point):
     if per_point is not None:
         _chk(per_point, "interval", _f32)
     e, a = torch.empty_like(density), torch.empty_like(density)
-    _lib.check(_lib.lib().esr_raw2alpha(_lib.ptr(density), C.c_float(float(shift)), C.c_float(float(interval)),
-                                        _lib.ptr(per_point) if per_point is not None else None, C.c_int64(density.shape[0]),
+    _lib.check(_lib.lib().esr_raw2alpha(_lib.ptr(density), float(shift), float(interval),
+                                        _lib.ptr(per_point) if per_point is not None else None, density.shape[0],
                                         _lib.ptr(e), _lib.ptr(a), _lib.stream_ptr(density.device)), "esr_raw2alpha")
     return [e, a]
 
@@ -226,8 +224,8 @@ def _raw2alpha_bwd(exp, grad_back, interval, per_point):
     if per_point is not None:
         _chk(per_point, "interval", _f32)
     g = torch.empty_like(exp)
-    _lib.check(_lib.lib().esr_raw2alpha_bwd(_lib.ptr(exp), _lib.ptr(grad_back), C.c_float(float(interval)),
-                                            _lib.ptr(per_point) if per_point is not None else None, C.c_int64(exp.shape[0]),
+    _lib.check(_lib.lib().esr_raw2alpha_bwd(_lib.ptr(exp), _lib.ptr(grad_back), float(interval),
+                                            _lib.ptr(per_point) if per_point is not None else None, exp.shape[0],
                                             _lib.ptr(g), _lib.stream_ptr(exp.device)), "esr_raw2alpha_bwd")
     return g
 
@@ -255,6 +253,6 @@ def total_variation_add_grad_new(param, grad, mask, wx, wy, wz, dense_mode):
     for t, n in ((param, "param"), (grad, "grad"), (mask, "mask")):
         _chk(t, n, _f32)
     _lib.check(_lib.lib().esr_tv_add_grad_masked(
-        _lib.ptr(param), _lib.ptr(grad), _lib.ptr(mask), C.c_float(float(wx)), C.c_float(float(wy)), C.c_float(float(wz)),
-        C.c_int64(param.shape[2]), C.c_int64(param.shape[3]), C.c_int64(param.shape[4]), C.c_int64(param.numel()),
-        C.c_int(1 if dense_mode else 0), _lib.stream_ptr(param.device)), "esr_tv_add_grad_masked")
+        _lib.ptr(param), _lib.ptr(grad), _lib.ptr(mask), float(wx), float(wy), float(wz),
+        param.shape[2], param.shape[3], param.shape[4], param.numel(),
+        1 if dense_mode else 0, _lib.stream_ptr(param.device)), "esr_tv_add_grad_masked")

@@ -53,7 +53,7 @@ class CoarseEngine(FineEngine):
         sm = torch.empty_like(sdf)
         gg = torch.empty(*dims, 3, dtype=torch.float32, device=dev)
         self._run("gauss3d_fwd", L.esr_gauss3d_fwd, _lib.ptr(sdf), kernel_w, ksize, *dims, _lib.ptr(sm), s)
-        self._run("central_grad_fwd", L.esr_central_grad_fwd, _lib.ptr(sdf), *dims, C.c_float(voxel_size),
+        self._run("central_grad_fwd", L.esr_central_grad_fwd, _lib.ptr(sdf), *dims, voxel_size,
                   _lib.ptr(gg), s)
         cnt3 = torch.empty(n, dtype=torch.int32, device=dev)
         off3 = torch.empty(n, dtype=torch.int32, device=dev)
@@ -152,7 +152,7 @@ class CoarseEngine(FineEngine):
                 self._run(f"mlp_wgrad({net})", self.mlp_wgrad, KIND_COARSE, _lib.ptr(b["X"]), crow, H, dZ,
                           _lib.ptr(b[f"{net}.dz"]), 0, t1, _lib.ptr_array(grads[f"{net}_w"]),
                           _lib.ptr_array(grads[f"{net}_b"]), _lib.ptr(self.wgrad_scratch),
-                          C.c_int64(self.wgrad_scratch.numel()), s)
+                          self.wgrad_scratch.numel(), s)
             self._run("feat_bwd", L.esr_coarse_feat_bwd, sp, _lib.ptr(bt["rays_o"]), _lib.ptr(bt["rays_d"]),
                       _lib.ptr(bt["viewdirs"]), _lib.ptr(b["rec_ray"]), _lib.ptr(b["rec_step"]), Ton, T, _lib.ptr(b["X"]),
                       _lib.ptr(b["gnorm"]), _lib.ptr(b["off.dX"]), _lib.ptr(b["emo.dX"]), _lib.ptr(g_gg),
@@ -168,7 +168,7 @@ class CoarseEngine(FineEngine):
         self._run("march_bwd", L.esr_march_bwd, march, s)
         self._run("gauss3d_bwd", L.esr_gauss3d_bwd, _lib.ptr(g_sm), ctx["kernel_w"], ctx["ksize"], *dims,
                   _lib.ptr(grads["sdf"]), s)
-        self._run("central_grad_bwd", L.esr_central_grad_bwd, _lib.ptr(g_gg), *dims, C.c_float(ctx["voxel"]),
+        self._run("central_grad_bwd", L.esr_central_grad_bwd, _lib.ptr(g_gg), *dims, ctx["voxel"],
                   _lib.ptr(grads["sdf"]), s)
 
 

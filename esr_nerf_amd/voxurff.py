@@ -323,8 +323,8 @@ class VoxurfF(ForwardSwitch, nn.Module):
         st, g = self._tv_state(), self.sdf.grid
         X, Y, Z = g.shape[2:]
         _lib.check(_lib.lib().esr_smooth_grad_tv_fwd(
-            _lib.ptr(g.detach()), _lib.ptr(st["mask"]), st["w27"], C.c_float(st["bias"]), X, Y, Z,
-            C.c_float(self._voxel_size_f), C.c_int64(st["count"]), C.c_float(weight), _lib.ptr(st["work"]),
+            _lib.ptr(g.detach()), _lib.ptr(st["mask"]), st["w27"], st["bias"], X, Y, Z,
+            self._voxel_size_f, st["count"], weight, _lib.ptr(st["work"]),
             _lib.ptr(loss_out), _lib.stream_ptr(g.device)), "esr_smooth_grad_tv_fwd")
 
     def smooth_grad_tv_bwd(self, weight: float, grad_sdf: torch.Tensor, grad_out: Optional[torch.Tensor] = None):
@@ -334,7 +334,7 @@ class VoxurfF(ForwardSwitch, nn.Module):
         st = self._tv_state()
         X, Y, Z = self.sdf.grid.shape[2:]
         _lib.check(_lib.lib().esr_smooth_grad_tv_bwd(
-            _lib.ptr(st["work"]), X, Y, Z, C.c_float(self._voxel_size_f), C.c_int64(st["count"]), C.c_float(weight),
+            _lib.ptr(st["work"]), X, Y, Z, self._voxel_size_f, st["count"], weight,
             _lib.ptr(grad_out), _lib.ptr(grad_sdf), _lib.stream_ptr(grad_sdf.device)), "esr_smooth_grad_tv_bwd")
 
     def sdf_total_variation_add_grad(self, weight: float, dense_mode: bool):

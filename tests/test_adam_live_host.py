@@ -180,12 +180,8 @@ def test_environment_switch_reaches_the_optimizer(monkeypatch):
 def test_header_declares_the_live_entries_and_ctypes_agrees():
     from esr_nerf_amd import _lib
     header = open(os.path.join(ROOT, "include", "esr_hip.h")).read()
-    for name in ("esr_adam_step_live", "esr_brick_live_from_moments"):
-        m = re.search(r"^int " + name + r"\s*\(([^;]*)\);", header, re.M)
-        assert m, name
-        assert name in _lib.EXPORTS
-        res, args = _lib.SIGNATURES[name]
-        assert len(args) == len(m.group(1).split(",")), name
+    # the names only: tests/test_host.py checks every entry's restype and argument types against the header text
+    assert {"esr_adam_step_live", "esr_brick_live_from_moments"} <= set(_lib.EXPORTS)
     assert "weight_decay" not in re.search(r"^int esr_adam_step_live\s*\(([^;]*)\);", header, re.M).group(1)
 
 

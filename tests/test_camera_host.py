@@ -146,12 +146,9 @@ def test_misuse_is_refused_with_a_message():
 
 def test_header_declares_the_camera_entry_points_and_ctypes_agrees():
     header = open(os.path.join(ROOT, "include", "esr_hip.h")).read()
+    # the names only: tests/test_host.py checks every entry's restype and argument types against the header text
     for name in ENTRIES:
-        m = re.search(r"^int " + name + r"\s*\(([^;]*)\);", header, re.M)
-        assert m, name
-        assert name in _lib.EXPORTS
-        res, args = _lib.SIGNATURES[name]
-        assert res is ctypes.c_int and len(args) == len(m.group(1).split(",")), name
+        assert name in _lib.EXPORTS and _lib.SIGNATURES[name][0] is ctypes.c_int, name
     assert int(re.search(r"#define ESR_ABI_VERSION (\d+)", header).group(1)) == _lib.ABI_VERSION
     for name, val in (("ESR_CAMERA_LDS_VIEWS", _lib.CAMERA_LDS_VIEWS), ("ESR_CAMERA_BOUNDS_BLOCKS", _lib.CAMERA_BOUNDS_BLOCKS)):
         assert int(re.search(r"#define " + name + r" (\d+)", header).group(1)) == val

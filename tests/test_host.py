@@ -31,28 +31,64 @@ def test_library_loads_and_exports_every_header_symbol():
     assert L.esr_mlp_packed_floats(0) > 0 and L.esr_mlp_packed_floats(7) < 0     # bad kind -> error code
 
 
-def test_ctypes_structs_match_the_c_layout():
+# the test's own reading of the header's prototypes (not _lib's parser): return type, name, parameter list
+PROTOTYPES = re.findall(r"^\s*(int|int64_t|const char \*)\s*(esr_\w+)\s*\(([^)]*)\)\s*;",
+                        re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "esr_hip.h")).read(), flags=re.S), re.M)
+C_TYPES = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+           "double": ctypes.c_double, "const char *": ctypes.c_char_p}
+
+
+@pytest.mark.parametrize("res, name, params", PROTOTYPES, ids=[p[1] for p in PROTOTYPES])
+def test_every_entry_carries_the_signature_the_header_declares(res, name, params):
+    """restype, arity and the exact type of every argument: scalars as declared, every pointer a c_void_p except the five that
+    stay typed (the march struct, the two [host] boxes)."""
     from esr_nerf_amd import _lib
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "esr_hip.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu",'
-           'sizeof(esr_scene_t),sizeof(esr_plan_t),sizeof(esr_mlp_weights_t),offsetof(esr_scene_t,grad_feat),'
-           'offsetof(esr_scene_t,near_),sizeof(esr_act_job_t),offsetof(esr_act_job_t,ex_col0),sizeof(esr_gather_job_t),'
-           'offsetof(esr_gather_job_t,out),sizeof(esr_pair_job_t),offsetof(esr_pair_job_t,gb),sizeof(esr_lts_gather_t));return 0;}')
+    params = [" ".join(p.split()) for p in params.split(",") if p.strip() != "void"]
+    want = [ctypes.c_void_p if "*" in p else C_TYPES[p.rsplit(" ", 1)[0]] for p in params]
+    typed = {"esr_march_count": (0, _lib.EsrMarch), "esr_march_fill": (0, _lib.EsrMarch), "esr_march_bwd": (0, _lib.EsrMarch),
+             "esr_nonempty_mask": (4, ctypes.c_float), "esr_density_bounds": (4, ctypes.c_float)}
+    if name in typed:
+        i, target = typed[name]
+        assert want[i] is ctypes.c_void_p
+        want[i] = ctypes.POINTER(target)
+    fn = getattr(_lib.lib(), name)
+    assert fn.restype is C_TYPES[res]
+    assert len(fn.argtypes) == len(params) and list(fn.argtypes) == want
+    assert _lib.SIGNATURES[name] == (C_TYPES[res], want)
+
+
+def test_a_bare_python_integer_reaches_an_int64_parameter_intact():
+    """Both calls return from the host-side checks of esr_cd_hash_insert (nothing is launched, no pointer is read): a capacity of
+    2^32 is a power of two only when all 64 bits arrive, and 2^31 keys are ESR_ECAP only when they arrive as 2^31."""
+    from esr_nerf_amd import _lib
+    L = _lib.lib()
+    assert L.esr_cd_hash_insert(None, 0, 1 << 32, None, None, None) == 0
+    p = ctypes.addressof((ctypes.c_int64 * 2)())
+    assert L.esr_cd_hash_insert(p, 1 << 31, 1 << 32, p, None, None) == -2
+
+
+def test_ctypes_structs_match_the_c_layout():
+    """sizeof and every field's offsetof of every struct _lib mirrors, against the C compiler's (esr_bvh_node_t has no class:
+    tests/test_raycast_host.py pins its layout)."""
+    from esr_nerf_amd import _lib
+    structs = {re.sub(r"(?<!^)(?=[A-Z])", "_", c.__name__).lower() + "_t": c for c in vars(_lib).values()
+               if isinstance(c, type) and issubclass(c, ctypes.Structure) and c is not ctypes.Structure}
+    header = open(os.path.join(ROOT, "include", "esr_hip.h")).read()
+    assert set(structs) | {"esr_bvh_node_t"} == set(re.findall(r"^}\s*(esr_\w+_t)\s*;", header, re.M)) and len(structs) >= 21
+    exprs = [e for t, c in structs.items() for e in [f"sizeof({t})"] + [f"offsetof({t},{f[0]})" for f in c._fields_]]
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "esr_hip.h"\nint main(){\n' +
+           "".join(f'printf("%zu\\n",{e});\n' for e in exprs) + "return 0;}\n")
     with tempfile.TemporaryDirectory() as d:
         c = os.path.join(d, "t.c")
         open(c, "w").write(src)
         exe = os.path.join(d, "t")
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        sizes = [int(v) for v in subprocess.check_output([exe]).split()]
-    assert sizes[0] == ctypes.sizeof(_lib.EsrScene)
-    assert sizes[1] == ctypes.sizeof(_lib.EsrPlan)
-    assert sizes[2] == ctypes.sizeof(_lib.EsrMlpWeights)
-    assert sizes[3] == _lib.EsrScene.grad_feat.offset
-    assert sizes[4] == _lib.EsrScene.near_.offset
-    # round 4: the job structs of the batched glue launches
-    assert sizes[5] == ctypes.sizeof(_lib.EsrActJob) and sizes[6] == _lib.EsrActJob.ex_col0.offset
-    assert sizes[7] == ctypes.sizeof(_lib.EsrGatherJob) and sizes[8] == _lib.EsrGatherJob.out.offset
-    assert sizes[9] == ctypes.sizeof(_lib.EsrPairJob) and sizes[10] == _lib.EsrPairJob.gb.offset
-    assert sizes[11] == ctypes.sizeof(_lib.EsrLtsGather)
+        got = dict(zip(exprs, (int(v) for v in subprocess.check_output([exe]).split())))
+    assert len(got) == len(exprs)
+    for t, c in structs.items():
+        assert got[f"sizeof({t})"] == ctypes.sizeof(c), t
+        for f in c._fields_:
+            assert got[f"offsetof({t},{f[0]})"] == getattr(c, f[0]).offset, (t, f[0])
 
 
 def _cpu_model(**model_over):

@@ -237,12 +237,8 @@ def test_rgb_lpips_refuses_without_weights_and_for_vgg():
 # ---- the C ABI ------------------------------------------------------------------------------------------------------------
 def test_header_declares_the_lpips_entry_points_and_ctypes_agrees():
     header = open(os.path.join(ROOT, "include", "esr_hip.h")).read()
-    for name in ENTRIES:
-        m = re.search(r"^(int|int64_t) " + name + r"\s*\(([^;]*)\);", header, re.M)
-        assert m, name
-        assert name in _lib.EXPORTS
-        res, args = _lib.SIGNATURES[name]
-        assert res is (ctypes.c_int if m.group(1) == "int" else ctypes.c_int64) and len(args) == len(m.group(2).split(",")), name
+    # the names only: tests/test_host.py checks every entry's restype and argument types against the header text
+    assert set(ENTRIES) <= set(_lib.EXPORTS)
     assert int(re.search(r"#define ESR_ABI_VERSION (\d+)", header).group(1)) == _lib.ABI_VERSION == _lib.lib().esr_abi_version()
     assert int(re.search(r"#define ESR_CONV_KC (\d+)", header).group(1)) == 32
     assert int(re.search(r"#define ESR_METRICS_BLOCKS (\d+)", header).group(1)) == lpips._BLOCKS

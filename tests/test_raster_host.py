@@ -203,17 +203,9 @@ def test_source_masks_restatement_and_the_occlusion_mutant():
 def test_header_declares_the_raster_entry_points_and_ctypes_agrees():
     from esr_nerf_amd import _lib, raster, relight
     header = open(os.path.join(ROOT, "include", "esr_hip.h")).read()
+    # the names only: tests/test_host.py checks every entry's restype and argument types against the header text
     for name in ENTRIES:
-        m = re.search(r"^(int|int64_t) " + name + r"\s*\(([^;]*)\);", header, re.M)
-        assert m, name
-        assert name in _lib.EXPORTS
-        res, args = _lib.SIGNATURES[name]
-        assert res is ctypes.c_int and m.group(1) == "int" and len(args) == len(m.group(2).split(",")), name
-        for arg, decl in zip(args, m.group(2).split(",")):
-            decl = decl.strip()
-            want = ctypes.c_void_p if "*" in decl else {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
-                                                       "double": ctypes.c_double}[decl.split()[0]]
-            assert arg is want, (name, decl)
+        assert name in _lib.EXPORTS and _lib.SIGNATURES[name][0] is ctypes.c_int, name
     assert int(re.search(r"#define ESR_ABI_VERSION (\d+)", header).group(1)) == _lib.ABI_VERSION == _lib.lib().esr_abi_version()
     assert int(re.search(r"#define ESR_RELIGHT_MAX_COND (\d+)", header).group(1)) == relight.MAX_CONDITIONS
     assert raster.BIG_PX >= 1 and raster.Z_NEAR > 0

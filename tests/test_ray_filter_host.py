@@ -85,10 +85,7 @@ def test_large_set_marginal_share_is_within_the_cap():
 def test_header_declares_esr_ray_filter_and_ctypes_agrees():
     from esr_nerf_amd import _lib, rayfilter
     header = open(os.path.join(ROOT, "include", "esr_hip.h")).read()
-    m = re.search(r"^int esr_ray_filter\s*\(([^;]*)\);", header, re.M)
-    assert m
+    # the names only: tests/test_host.py checks every entry's restype and argument types against the header text
     assert "esr_ray_filter" in _lib.EXPORTS
-    res, args = _lib.SIGNATURES["esr_ray_filter"]
-    assert len(args) == len(m.group(1).split(","))
     for name, val in (("ESR_RAY_FILTER_MARCH", rayfilter.MODE_MARCH), ("ESR_RAY_FILTER_FIXED", rayfilter.MODE_FIXED)):
         assert int(re.search(r"#define " + name + r" (\d+)", header).group(1)) == val

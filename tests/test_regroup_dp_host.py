@@ -144,18 +144,9 @@ def test_a_sampler_of_many_ranks_is_still_refused_without_a_process_group():
 
 def test_header_declares_the_packed_entry_points_and_ctypes_agrees():
     header = open(os.path.join(ROOT, "include", "esr_hip.h")).read()
-    ctype_of = {"void *": ctypes.c_void_p, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "int": ctypes.c_int}
+    # the names only: tests/test_host.py checks every entry's restype and argument types against the header text
     for name in ENTRIES:
-        m = re.search(r"^int " + name + r"\s*\(([^;]*)\);", header, re.M)
-        assert m, name
-        assert name in _lib.EXPORTS
-        res, args = _lib.SIGNATURES[name]
-        declared = [" ".join(a.split()) for a in m.group(1).split(",")]
-        assert res is ctypes.c_int and len(args) == len(declared), name
-        for a, t in zip(declared, args):
-            kind = "void *" if "*" in a else a.rsplit(" ", 1)[0]     # every pointer travels as a void pointer
-            assert ctype_of[kind] is t, (name, a, t)
-        assert hasattr(_lib.lib(), name), name
+        assert name in _lib.EXPORTS and _lib.SIGNATURES[name][0] is ctypes.c_int and hasattr(_lib.lib(), name), name
     assert int(re.search(r"#define ESR_ABI_VERSION (\d+)", header).group(1)) == _lib.ABI_VERSION == _lib.lib().esr_abi_version()
     assert _lib.PARTITION_BLOCK % 64 == 0 and _lib.PARTITION_BLOCK // 64 == 16
 

@@ -135,12 +135,8 @@ def test_set_rows_refuses_nothing_and_changes_no_other_method():
 def test_header_declares_the_entry_points_and_ctypes_agrees():
     from esr_nerf_amd import _lib
     header = open(os.path.join(ROOT, "include", "esr_hip.h")).read()
-    for name in ("esr_mask_dilate", "esr_edit_label"):
-        m = re.search(r"^int " + name + r"\s*\(([^;]*)\);", header, re.M)
-        assert m, name
-        assert name in _lib.EXPORTS
-        res, args = _lib.SIGNATURES[name]
-        assert len(args) == len(m.group(1).split(",")), name
+    # the names only: tests/test_host.py checks every entry's restype and argument types against the header text
+    assert {"esr_mask_dilate", "esr_edit_label"} <= set(_lib.EXPORTS)
     m = re.search(r"#define ESR_RELIGHT_MAX_COND (\d+)", header)
     from esr_nerf_amd import relight
     assert int(m.group(1)) == relight.MAX_CONDITIONS
