@@ -135,6 +135,15 @@ class EsrRegroupStats(C.Structure):     # esr_regroup_stats_t
                [(n, C.c_float) for n in ("min_all", "max_all", "min_set", "max_set", "min_clear", "max_clear")]
 
 
+class EsrSurfaceLight(C.Structure):     # esr_surface_light_t
+    _fields_ = [("nodes", C.c_void_p), ("n_faces", C.c_int64), ("vertices", C.c_void_p), ("n_vertices", C.c_int64),
+                ("triangles", C.c_void_p), ("n_sources", C.c_int64), ("slots", C.c_int32), ("mode", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("l_point", "l_normal", "l_weight", "l_radiance", "l_face")] + \
+               [("n_points", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("p_point", "p_normal", "p_base", "p_rough", "p_metal", "p_wo")] + \
+               [("eps", C.c_double), ("out", C.c_void_p), ("seen", C.c_void_p)]
+
+
 class EsrMlpWeights(C.Structure):
     _fields_ = [("w", C.c_void_p * 4), ("b", C.c_void_p * 4)]
 

@@ -59,6 +59,30 @@ def dilate_masks(em_masks, ks: int) -> torch.Tensor:
     return out
 
 
+@torch.no_grad()
+def edit_emission(emit, modes, intensities, colors) -> torch.Tensor:
+    """The emission edit of the re-lighting fine-tune (esrnerf.py:427-441) on any emission values: ``emit`` float32 [n, 3],
+    ``modes`` int64 [n] (``LIGHT_MODES``: 0 off, 1 unchanged, 2 scaled by ``intensities`` [n], 3 hue and saturation
+    replaced by ``colors`` [n, 2] with the value kept, 4 both) -> a new float32 [n, 3] device tensor (``esr_emit_edit``, the
+    kernel the light-transport engine runs on its own points)."""
+    e = _device_f32(emit).clone()
+    if e.dim() != 2 or e.shape[1] != 3:
+        raise ValueError(f"edit_emission: emit is [n, 3], got {tuple(e.shape)}")
+    n, dev = int(e.shape[0]), e.device
+    if n >= 2 ** 31:
+        raise ValueError(f"edit_emission: {n} values exceed the kernel's 31-bit count")
+    if not isinstance(modes, torch.Tensor) or modes.dtype != torch.int64 or modes.shape != (n,) or modes.device != dev:
+        raise ValueError("edit_emission: modes is an int64 [n] tensor on the device of emit")
+    k, c = _device_f32(intensities, dev), _device_f32(colors, dev)
+    if k.shape != (n,) or c.shape != (n, 2) or k.device != dev or c.device != dev:
+        raise ValueError("edit_emission: intensities is [n] and colors [n, 2] (hue, saturation), on the device of emit")
+    if n:
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().esr_emit_edit(_lib.ptr(e), _lib.ptr(modes.contiguous()), _lib.ptr(k), _lib.ptr(c), n,
+                                                _lib.stream_ptr(dev)), "esr_emit_edit")
+    return e
+
+
 def label_edit_rays(esp, pose, focal, width, height, masks, em_modes, em_intensities=None, em_colors=None,
                     return_uv=False) -> Dict[str, torch.Tensor]:
     """pdra.py:988-1028 for all rays in one launch.  esp [n, 3] (``eval_esp``), pose [4, 4] camera-to-world (inverted on

@@ -15,6 +15,11 @@ fine.py:632) and knows emissive sources only per view, as the image masks ``any(
 ``write_surface_ply``  a binary PLY with the attributes per vertex and the source id per face (chamfer.read_ply reads the
                        mesh back)
 
+``source_lights``      the sources as area-weighted point lights at ``source_samples``' points, with edits applied
+``direct_light``       their light at surface points, shadowed by the surface, reflected once by the light-transport stage's
+                       Disney BRDF or as irradiance: one fused launch (csrc/surflight.hip, header section U)
+``lit_view``           the same for the pixels of a camera view
+
 Everything up to the file is device tensors; nothing here copies the mesh to the host.
 """
 from __future__ import annotations
@@ -214,6 +219,263 @@ def source_visibility(surface: Surface, report: SourceReport, points: torch.Tens
     return out
 
 
+MAX_LIGHT_SLOTS = 64                     # ESR_SURFACE_LIGHT_MAX_SLOTS: a source's sample slots sit in one wave
+
+
+@dataclass
+class SourceLights:
+    """The sources of a surface as point lights, slot-major as ``esr_surface_light`` takes them: Kp slots per source (a power
+    of two), of which the first ``n[s]`` are used"""
+    point: torch.Tensor                  # device float64 [S, Kp, 3]: the sample points (face centres)
+    normal: torch.Tensor                 # device float64 [S, Kp, 3]: the unit normal of the sample's face
+    weight: torch.Tensor                 # device float64 [S, Kp]: area_s / n_s, the area a sample stands for; 0 in an unused slot
+    radiance: torch.Tensor               # device float32 [S, Kp, 3]: the mean emission of the face's vertices, edited
+    face: torch.Tensor                   # device int32 [S, Kp]: the sample's face (the shadow segment never hits it)
+    n: torch.Tensor                      # device int64 [S]: the used slots of every source
+
+    def __len__(self):
+        return int(self.point.shape[0])
+
+    @property
+    def slots(self) -> int:
+        return int(self.point.shape[1])
+
+
+def _edit_tables(what, n_sources, edits, dev):
+    """per source: (mode int64 [S], intensity float32 [S], colour float32 [S, 2]) of ``raster.edit_view_data``'s edit dicts;
+    a source in no edit is unchanged.  Refuses before anything is launched."""
+    from .raster import EDIT_MODES, _conditions
+    from .relight import LIGHT_MODES
+    modes, inten, cols = [LIGHT_MODES["on"]] * n_sources, [1.0] * n_sources, [[0.0, 0.0] for _ in range(n_sources)]
+    groups = []
+    for e in edits:
+        if not isinstance(e, dict) or e.get("mode") not in EDIT_MODES:
+            raise ValueError(f"{what}: an edit is a dict whose mode is one of {EDIT_MODES}")
+        col = [float(c) for c in e.get("color", (0.0, 0.0, 0.0))]
+        if len(col) not in (2, 3):
+            raise ValueError(f"{what}: a colour has 2 or 3 components, got {len(col)}")
+        groups.append(list(e.get("sources", ())))
+    try:
+        cond = _conditions(n_sources, groups)
+    except ValueError as err:
+        raise ValueError(f"{what}: {err}") from None
+    for s in range(n_sources):
+        if cond[s] >= 0:
+            e = edits[int(cond[s])]
+            modes[s], inten[s] = LIGHT_MODES[e["mode"]], float(e.get("intensity", 1.0))
+            cols[s] = [float(c) for c in e.get("color", (0.0, 0.0, 0.0))][:2]
+    return (torch.tensor(modes, dtype=torch.int64).reshape(n_sources).to(dev),
+            torch.tensor(inten, dtype=torch.float32).reshape(n_sources).to(dev),
+            torch.tensor(cols, dtype=torch.float32).reshape(n_sources, 2).to(dev))
+
+
+@torch.no_grad()
+def source_lights(surface: Surface, report: SourceReport, samples: int = 16, edits=None) -> SourceLights:
+    """The sources of ``report`` as the point lights of ``direct_light``: the sample points and faces of ``source_samples``;
+    per sample the unit normal n / |n|, n = (b - a) x (c - a), of its face (float64, every operation its own launch, as in
+    ``source_samples``), the weight ``area_s / n_s`` (the area one sample stands for) and the radiance ((e_a + e_b) + e_c) *
+    (1 / 3) of the face's three vertex emissions (float32).  ``Kp``, the slots per source, is the next power of two >=
+    ``samples`` (at most 64 samples); the slots from ``n_s`` on have weight 0 and are never used.
+    ``edits``: the dicts of ``raster.edit_view_data`` (``sources``, ``mode``, ``intensity``, ``color``: hue and saturation
+    first), applied to every sample of their sources through ``relight.edit_emission``.  No read-back."""
+    samples = int(samples)
+    if samples < 1 or samples > MAX_LIGHT_SLOTS:
+        raise ValueError(f"source_lights: 1 .. {MAX_LIGHT_SLOTS} samples per source, got {samples}")
+    S, dev = len(report), surface.vertices.device
+    tables = _edit_tables("source_lights", S, edits, dev) if edits else None
+    kp = 1
+    while kp < samples:
+        kp *= 2
+    face, point, n = source_samples(surface, report, samples)
+    v, t = surface.vertices, surface.triangles
+    f = face.long()
+    if t.shape[0]:
+        a, b, c = (v[t[f, k]] for k in range(3))                          # [S, samples, 3]
+        em = surface.attrs["emission"].float()
+        ea, eb, ec = (em[t[f, k]] for k in range(3))
+    else:
+        a = b = c = torch.zeros(S, samples, 3, dtype=torch.float64, device=dev)
+        ea = eb = ec = torch.zeros(S, samples, 3, dtype=torch.float32, device=dev)
+    e1, e2 = b - a, c - a
+    n0 = e1[..., 1] * e2[..., 2] - e1[..., 2] * e2[..., 1]
+    n1 = e1[..., 2] * e2[..., 0] - e1[..., 0] * e2[..., 2]
+    n2 = e1[..., 0] * e2[..., 1] - e1[..., 1] * e2[..., 0]
+    length = torch.sqrt((n0 * n0 + n1 * n1) + n2 * n2)
+    normal = torch.stack([n0, n1, n2], -1) / length[..., None]
+    radiance = ((ea + eb) + ec) * (1.0 / 3.0)
+    used = torch.arange(samples, device=dev)[None, :] < n[:, None]       # [S, samples]
+    weight = (report.area.double() / n.clamp(min=1).double())[:, None].expand(S, samples)
+    if tables is not None and S:
+        from .relight import edit_emission
+        modes, inten, cols = (x[:, None].expand(S, samples, *x.shape[1:]).reshape(S * samples, *x.shape[1:]).contiguous()
+                              for x in tables)
+        radiance = edit_emission(radiance.reshape(-1, 3), modes, inten, cols).reshape(S, samples, 3)
+
+    def slots(x, fill):
+        out = torch.full((S, kp) + tuple(x.shape[2:]), fill, dtype=x.dtype, device=dev)
+        out[:, :samples] = torch.where(used.reshape(S, samples, *([1] * (x.dim() - 2))), x, torch.full_like(x, fill))
+        return out.contiguous()
+    return SourceLights(slots(point, 0.0), slots(normal, 0.0), slots(weight, 0.0), slots(radiance, 0.0), slots(face, -1), n)
+
+
+def _light_input(what, name, x, shape, dev, dtypes=(torch.float32, torch.float64)):
+    if not isinstance(x, torch.Tensor) or x.device != dev or x.dtype not in dtypes or tuple(x.shape) != shape:
+        raise ValueError(f"{what}: {name} must be a float {list(shape)} tensor on the surface's device")
+    return x
+
+
+@torch.no_grad()
+def direct_light(surface: Surface, lights: SourceLights, points: torch.Tensor, normals: torch.Tensor, basecolor=None,
+                 roughness=None, metallic=None, wo=None, bvh=None, per_source: bool = False, eps: float = 1e-6,
+                 return_seen: bool = False):
+    """The light of the sources ``lights`` (``source_lights``) at the surface points ``points`` [P, 3] with the unit shading
+    normals ``normals`` [P, 3], shadowed by the surface, in one fused launch (``esr_surface_light``, section U of
+    include/esr_hip.h): per point, source and sample the geometric term ``G = cos_l A / max(r^2, A)`` in float64, the shadow
+    segment of ``raycast.occluded_segments`` (``eps``, the sample's own face skipped) only where G is not zero, and
+
+    with ``wo`` [P, 3] (unit, towards the viewer), ``basecolor`` [P, 3], ``roughness`` [P] and ``metallic`` [P]: the radiance
+    reflected towards ``wo`` by the Disney BRDF of the light-transport stage (the model's ``emo`` component, one bounce);
+    with ``wo=None``: the irradiance, sum of cos_x G E (no BRDF, no view).
+
+    -> float32 [P, 3], the sum over the sources (in float64, in source order, rounded once), or with ``per_source`` the
+    kernel's [P, S, 3]: an intensity edit of a source is a re-weighting of that.  ``return_seen`` adds uint8 [P, S, Kp]: 0 a
+    sample that contributes nothing unshadowed (unused, behind the point or the source facing away), 1 seen, 2 shadowed.
+
+    A sample is a point light standing for the area A = area_s / n_s; the clamp max(r^2, A) keeps it bounded, so within
+    about one sample spacing of a source the estimate is LOW (far from it, it converges on the area integral).  ``bvh``: the
+    ``raycast.Bvh`` of the surface, built here when None.  The same input gives the same bytes on every call; no read-back."""
+    from . import _lib, raycast
+    what = "direct_light"
+    v = surface.vertices
+    dev = v.device
+    if not isinstance(lights, SourceLights):
+        raise ValueError(f"{what}: lights is a SourceLights (source_lights)")
+    S, kp = len(lights), lights.slots
+    if kp < 1 or kp > MAX_LIGHT_SLOTS or kp & (kp - 1):
+        raise ValueError(f"{what}: {kp} slots per source; a power of two up to {MAX_LIGHT_SLOTS}")
+    for name, x, shape, dt in (("point", lights.point, (S, kp, 3), torch.float64), ("normal", lights.normal, (S, kp, 3), torch.float64),
+                               ("weight", lights.weight, (S, kp), torch.float64), ("radiance", lights.radiance, (S, kp, 3), torch.float32),
+                               ("face", lights.face, (S, kp), torch.int32)):
+        if not isinstance(x, torch.Tensor) or x.device != dev or x.dtype != dt or tuple(x.shape) != shape:
+            raise ValueError(f"{what}: lights.{name} must be a {dt} {list(shape)} tensor on the surface's device")
+    if not isinstance(points, torch.Tensor) or points.dim() != 2:
+        raise ValueError(f"{what}: points must be a float [P, 3] tensor on the surface's device")
+    P = int(points.shape[0])
+    _light_input(what, "points", points, (P, 3), dev)
+    _light_input(what, "normals", normals, (P, 3), dev)
+    if P >= 2 ** 31 or S >= 2 ** 31:
+        raise ValueError(f"{what}: {P} points and {S} sources exceed the kernel's 31-bit counts")
+    if not 0.0 <= float(eps) < 0.5:
+        raise ValueError(f"{what}: eps is in [0, 0.5), got {eps}")
+    mode = 1 if wo is None else 0
+    mat = [None] * 4
+    if mode == 0:
+        if basecolor is None or roughness is None or metallic is None:
+            raise ValueError(f"{what}: with wo the reflection needs basecolor, roughness and metallic")
+        mat = [_light_input(what, name, x, shape, dev).float().contiguous()
+               for name, x, shape in (("basecolor", basecolor, (P, 3)), ("roughness", roughness, (P,)), ("metallic", metallic, (P,)),
+                                      ("wo", wo, (P, 3)))]
+    if bvh is None:
+        bvh = raycast.build(v, surface.triangles)
+    elif not isinstance(bvh, raycast.Bvh) or bvh.vertices.device != dev:
+        raise ValueError(f"{what}: bvh is the raycast.Bvh of the surface")
+    out = torch.zeros(P, S, 3, dtype=torch.float32, device=dev)
+    seen = torch.zeros(P, S, kp, dtype=torch.uint8, device=dev) if return_seen else None
+    if P and S:
+        pts, nrm = points.double().contiguous(), normals.float().contiguous()
+        arrays = [x.contiguous() for x in (lights.point, lights.normal, lights.weight, lights.radiance, lights.face)]
+        args = _lib.EsrSurfaceLight(
+            nodes=_lib.ptr(bvh.nodes), n_faces=bvh.n_faces, vertices=_lib.ptr(bvh.vertices), n_vertices=int(bvh.vertices.shape[0]),
+            triangles=_lib.ptr(bvh.triangles), n_sources=S, slots=kp, mode=mode,
+            l_point=_lib.ptr(arrays[0]), l_normal=_lib.ptr(arrays[1]), l_weight=_lib.ptr(arrays[2]), l_radiance=_lib.ptr(arrays[3]),
+            l_face=_lib.ptr(arrays[4]), n_points=P, p_point=_lib.ptr(pts), p_normal=_lib.ptr(nrm), p_base=_lib.ptr(mat[0]),
+            p_rough=_lib.ptr(mat[1]), p_metal=_lib.ptr(mat[2]), p_wo=_lib.ptr(mat[3]), eps=float(eps), out=_lib.ptr(out),
+            seen=_lib.ptr(seen))
+        import ctypes
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().esr_surface_light(ctypes.byref(args), _lib.stream_ptr(dev)), "esr_surface_light")
+    if not per_source:
+        total = torch.zeros(P, 3, dtype=torch.float64, device=dev)
+        for s in range(S):                                                # (source order: the same bytes whatever torch's sum does)
+            total = total + out[:, s].double()
+        out = total.float()
+    return (out, seen) if return_seen else out
+
+
+def _hit_points(surface: Surface, hit, d):
+    """What ``lit_view`` knows at the nearest hits ``hit`` (``raycast.Hits``) of the rays with the directions ``d``: the point
+    (float64, NaN where the ray misses: such a point is lit by nothing), the unit shading normal, the interpolated
+    attributes and ``wo``.  The barycentric weights are (1 - u) - v, u, v; every operation is its own launch."""
+    v, t = surface.vertices, surface.triangles
+    tri = t[hit.face.clamp(min=0).long()]                                  # [N, 3]
+    bu, bv = hit.bary[:, 0], hit.bary[:, 1]
+    b64 = torch.stack([(1.0 - bu) - bv, bu, bv], 1)                        # the weights of the face's three vertices
+    b32 = b64.float()
+
+    def at(x, b):
+        x = x.reshape(x.shape[0], -1)
+        return (x[tri[:, 0]] * b[:, 0:1] + x[tri[:, 1]] * b[:, 1:2]) + x[tri[:, 2]] * b[:, 2:3]
+
+    def unit(x):
+        return x / torch.sqrt((x[:, 0] * x[:, 0] + x[:, 1] * x[:, 1]) + x[:, 2] * x[:, 2]).clamp(min=1e-12)[:, None]
+    nan = torch.full((1, 3), float("nan"), dtype=torch.float64, device=v.device)
+    x = torch.where((hit.face >= 0)[:, None], at(v, b64), nan)
+    a = {k: at(surface.attrs[k].float(), b32) for k in ("normal", "basecolor", "roughness", "metallic", "emission")}
+    return x, unit(a["normal"]), a, (-unit(d)).float()
+
+
+@torch.no_grad()
+def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: int = 16, edits=None, bvh=None):
+    """View ``view`` of ``cams`` lit by the (edited) sources, without an optimiser step: the nearest face of every pixel
+    (the rays and the walk of ``raycast.cast_cameras``), the vertex attributes interpolated with the hit's barycentrics in
+    torch (the normal normalised again), ``wo`` = minus the unit pixel ray, and ``direct_light`` with ``source_lights(surface,
+    report, samples, edits)``.  -> dict of
+
+    ``lin/reflect`` float32 [H, W, 3]  the sources' light reflected once towards the camera (the model's ``emo`` component)
+    ``lin/emit``    float32 [H, W, 3]  the interpolated emission, edited, where the pixel's face belongs to a source
+    ``face``        int32 [H, W]       as ``cast_cameras``; -1 where the ray misses
+    ``depth``       float64 [H, W]     as ``cast_cameras``; +inf where the ray misses
+
+    A pixel that misses is 0 in both images.  The linear image of the edited scene is ``off + lin/emit + lin/reflect``
+    where ``off`` -- the light of the environment, which no source edit changes -- stays the volumetric renderer's.  The
+    near-field limit of ``direct_light`` applies.  Nothing is read back."""
+    from . import raycast
+    from .relight import edit_emission
+    what = "lit_view"
+    if isinstance(view, bool) or not isinstance(view, int) or not 0 <= view < cams.n_views:
+        raise ValueError(f"{what}: view {view!r} of a set of {cams.n_views}")
+    samples = int(samples)
+    if samples < 1 or samples > MAX_LIGHT_SLOTS:
+        raise ValueError(f"{what}: 1 .. {MAX_LIGHT_SLOTS} samples per source, got {samples}")
+    v, t = surface.vertices, surface.triangles
+    dev, S = v.device, len(report)
+    if cams.device != dev:
+        raise ValueError(f"{what}: the surface and the cameras are on one device")
+    tables = _edit_tables(what, S, edits, dev) if edits else None
+    if bvh is None:
+        bvh = raycast.build(v, t)
+    lights = source_lights(surface, report, samples, edits)
+    H, W = cams.height, cams.width
+    o, d, _ = raycast.pixel_rays(cams, view)
+    hit = raycast.cast(bvh, o, d)
+    if not t.shape[0]:                                                     # (no face: every ray misses)
+        black = torch.zeros(H, W, 3, dtype=torch.float32, device=dev)
+        return {"lin/reflect": black, "lin/emit": black.clone(), "face": hit.face.reshape(H, W), "depth": hit.t.reshape(H, W)}
+    got = hit.face >= 0
+    x, normal, a, wo = _hit_points(surface, hit, d)
+    reflect = direct_light(surface, lights, x, normal, a["basecolor"], a["roughness"][:, 0], a["metallic"][:, 0], wo, bvh=bvh)
+    src = report.face_source[hit.face.clamp(min=0).long()]
+    lit = got & (src >= 0)
+    emit = a["emission"].contiguous()
+    if tables is not None and S:
+        sid = src.clamp(min=0).long()
+        emit = edit_emission(emit, tables[0][sid].contiguous(), tables[1][sid].contiguous(), tables[2][sid].contiguous())
+    zero = torch.zeros(1, 3, dtype=torch.float32, device=dev)
+    return {"lin/reflect": torch.where(got[:, None], reflect, zero).reshape(H, W, 3),
+            "lin/emit": torch.where(lit[:, None], emit, zero).reshape(H, W, 3),
+            "face": hit.face.reshape(H, W), "depth": hit.t.reshape(H, W)}
+
+
 VERTEX_PROPERTIES = ["x", "y", "z", "nx", "ny", "nz", "basecolor_r", "basecolor_g", "basecolor_b", "roughness", "metallic",
                      "emission_r", "emission_g", "emission_b"]
 
@@ -255,4 +517,4 @@ def write_surface_ply(path, surface: Surface, face_source: Optional[torch.Tensor
 
 
 __all__ = ["Surface", "SourceReport", "extract_surface", "emissive_sources", "simplify_surface", "write_surface_ply",
-           "source_samples", "source_visibility", "VERTEX_PROPERTIES"]
+           "source_samples", "source_visibility", "SourceLights", "source_lights", "direct_light", "lit_view", "VERTEX_PROPERTIES"]

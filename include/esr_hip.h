@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 43
+#define ESR_ABI_VERSION 44
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -1763,6 +1763,75 @@ int esr_bvh_cast(const esr_bvh_node_t *nodes, int64_t n_faces, const double *ver
                  const int64_t *triangles, const double *rays_o, const double *rays_d, int64_t n_rays,
                  const double *t_min, const double *t_max, double t_min_all, double t_max_all, const int32_t *skip_face,
                  int32_t any_hit, int32_t *face, double *t, double *bary, uint8_t *hit, int32_t *stats, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * U. Surface lighting (esr_nerf_amd/sources.py: direct_light, lit_view): the light that leaves the emissive sources of the
+ *    exported surface and reaches a surface point directly -- reflected once by the Disney BRDF of the light-transport
+ *    stage (the model's `emo` component, app/fine/model/esrnerf.py:565-572, app/utils/pbr/functions.py:108-173) or as
+ *    irradiance.  An addition: the reference has no counterpart on a mesh
+ * ------------------------------------------------------------------------- */
+
+#define ESR_SURFACE_LIGHT_MAX_SLOTS 64   /* most sample slots of a source (ESR_ECAP beyond it: a source's slots sit in one wave) */
+
+/*
+ * Scene.  nodes / n_faces / vertices / n_vertices / triangles: the tree and the mesh exactly as esr_bvh_cast takes them (the
+ * same pointer and alignment rules, the same n_faces == 0, 1, > 1 cases).
+ * Lights.  n_sources sources (S) of `slots` sample slots each (Kp): a power of two, 1 <= Kp <= 64, the same for every
+ * source; slot-major arrays
+ *   l_point f64 [S,Kp,3]   l_normal f64 [S,Kp,3] (unit length)   l_weight f64 [S,Kp]   l_radiance f32 [S,Kp,3]   l_face i32 [S,Kp]
+ * A slot with l_weight == 0 is unused: nothing else of it is read.
+ * Points.  n_points points (P): p_point f64 [P,3], p_normal f32 [P,3] (unit length); in mode 0 also p_base f32 [P,3], p_rough
+ * f32 [P], p_metal f32 [P] and p_wo f32 [P,3], the unit direction towards the viewer (unused and may be NULL in mode 1).
+ *
+ * Per point x (normal n), source s and slot k with point y, normal g, weight A, radiance E, face f -- binary64, every
+ * operation rounded on its own (no contraction), in this order:
+ *   d = y - x;  r2 = (d0 d0 + d1 d1) + d2 d2;  r = sqrt(r2);  w_i = d_i / r;
+ *   cos_l = -((g0 w0 + g1 w1) + g2 w2);  cos_x = (n0 w0 + n1 w1) + n2 w2   (the binary32 normal widened)
+ *   the slot is SILENT -- it contributes +0.0 and no segment is walked -- if A == 0 or if any of r2 > 0, cos_l > 0,
+ *   cos_x > 0 is false (a NaN makes a comparison false).  Otherwise
+ *   G = (cos_l A) / max(r2, A)        (max of two numbers: the one that is not a NaN)
+ *   The clamp max(r2, A) is the usual bound of a point sample of an area light: within about one sample spacing of a
+ *   source the estimate is LOW.
+ *   occluded iff esr_bvh_cast's any-hit walk finds a face: o = x, d = d, eps < t <= 1 - eps (1 - eps rounded once),
+ *   skip_face = f.  If not occluded, per channel c
+ *     mode 0 (reflected radiance)  term_c = (((double)R_c (1 / (2 pi))) G) (double)E_c
+ *            R = the binary32 Disney reflection of the light-transport combine for base, rough, metal, n, wi = (float)w, wo:
+ *            it carries (n . wi) 2 pi, the weight of the hemisphere estimator, which 1 / (2 pi) (binary64, 1 / (2 pi) with
+ *            pi rounded to binary64) takes back out
+ *     mode 1 (irradiance)          term_c = (cos_x G) (double)E_c
+ * out f32 [P,S,3]: out[p,s,c] = the binary32 rounding of the balanced pairwise binary64 sum of the Kp terms of (p, s):
+ * slots 2 j and 2 j + 1 are added first, then adjacent pairs of those sums, and so on.  The order is fixed and there are
+ * no atomics: the same input gives the same bytes on every call.
+ * seen u8 [P,S,Kp] or NULL: 0 silent, 1 walked and not occluded, 2 walked and occluded.
+ *
+ * n_points == 0 or n_sources == 0 succeeds and touches no pointer.  ESR_EINVAL: a NULL struct, a negative size, a mode
+ * other than 0 and 1, slots < 1 or not a power of two, eps not in [0, 0.5), a NULL or misaligned pointer (f64 / i64: 8
+ * bytes, nodes: 16, the rest: 4).  ESR_ECAP: a size >= 2^31, slots > ESR_SURFACE_LIGHT_MAX_SLOTS.  Nothing is launched in
+ * either case.  One launch on `stream`; nothing waits on the host.
+ * Layout: Kp adjacent lanes work on one (point, source), a wave holds 64 / Kp points; the point stays in registers over the
+ * sources; nothing of size P S Kp reaches memory but `seen`.
+ */
+typedef struct esr_surface_light {
+    const esr_bvh_node_t *nodes;
+    int64_t n_faces;
+    const double *vertices;
+    int64_t n_vertices;
+    const int64_t *triangles;
+    int64_t n_sources;
+    int32_t slots;
+    int32_t mode;
+    const double *l_point, *l_normal, *l_weight;
+    const float *l_radiance;
+    const int32_t *l_face;
+    int64_t n_points;
+    const double *p_point;
+    const float *p_normal, *p_base, *p_rough, *p_metal, *p_wo;
+    double eps;
+    float *out;
+    uint8_t *seen;
+} esr_surface_light_t;
+
+int esr_surface_light(const esr_surface_light_t *args, void *stream);
 
 #ifdef __cplusplus
 }
