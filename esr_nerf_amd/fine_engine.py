@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 
-KIND_RADIANCE, KIND_TONEMAP = 0, 1
+KIND_RADIANCE, KIND_TONEMAP = _lib.MLP_RADIANCE, _lib.MLP_TONEMAP
 HID = 192
 X_ROWS, DX_ROWS, XT_ROWS = 104, 64, 48
 

@@ -33,7 +33,7 @@ SCALE = (0.458, 0.448, 0.450)
 FEATURE_INDEX = (0, 3, 6, 8, 10)            # the convolutions' positions in torchvision's alexnet().features
 MIN_SIZE = 31                               # the smallest image side for which every tap is non-empty
 POOL_K, POOL_STRIDE = 3, 2
-_BLOCKS = 1024                              # ESR_METRICS_BLOCKS
+_BLOCKS = _lib.METRICS_BLOCKS
 
 
 def conv_out(size: int, k: int, stride: int, pad: int) -> int:

@@ -27,7 +27,7 @@ import torch
 from . import _lib
 from .fine_engine import DX_ROWS, KIND_RADIANCE, KIND_TONEMAP, X_ROWS, XT_ROWS, FineEngine, _follows_forward
 
-KIND_BRDF, KIND_EMIT = 2, 3
+KIND_BRDF, KIND_EMIT = _lib.MLP_BRDF, _lib.MLP_EMIT
 ACT_SOFTPLUS, ACT_SIGMOID = 0, 1
 
 

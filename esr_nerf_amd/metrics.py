@@ -21,8 +21,8 @@ import torch
 
 from . import _lib
 
-MAX_FILTER_SIZE = 33          # ESR_SSIM_MAX_TAPS
-_BLOCKS = 1024                # ESR_METRICS_BLOCKS
+MAX_FILTER_SIZE = _lib.SSIM_MAX_TAPS
+_BLOCKS = _lib.METRICS_BLOCKS
 
 
 def _dev(device=None):

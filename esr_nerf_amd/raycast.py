@@ -13,6 +13,7 @@ Nothing here reads anything back from the device; the answer is a function of th
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from dataclasses import dataclass
 from typing import NamedTuple, Optional
@@ -22,7 +23,7 @@ import torch
 from . import _lib
 from .mesh import _check_mesh
 
-NODE_WORDS = 16                          # an esr_bvh_node_t as int32 words: 12 of boxes, child[2], parent, pad
+NODE_WORDS = ctypes.sizeof(_lib.EsrBvhNode) // 4   # an esr_bvh_node_t as int32 words: 12 of boxes, child[2], parent, pad
 
 
 @dataclass

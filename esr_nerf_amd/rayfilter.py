@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 
-MODE_MARCH, MODE_FIXED = 0, 1          # ESR_RAY_FILTER_MARCH / ESR_RAY_FILTER_FIXED
+MODE_MARCH, MODE_FIXED = _lib.RAY_FILTER_MARCH, _lib.RAY_FILTER_FIXED
 
 
 def fixed_n_samples(renderer) -> int:

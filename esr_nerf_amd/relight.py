@@ -24,7 +24,7 @@ import torch
 from . import _lib
 
 LIGHT_MODES = {"off": 0, "on": 1, "i_change": 2, "c_change": 3, "ic_change": 4}      # utils2/utils.py:32-38
-MAX_CONDITIONS = 16                                                                  # ESR_RELIGHT_MAX_COND
+MAX_CONDITIONS = _lib.RELIGHT_MAX_COND
 EDIT_KEYS = ("em_colors", "em_intensities")
 
 

@@ -30,7 +30,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import mesh
+from . import _lib, mesh
 
 ATTR_KEYS = ("normal", "sdf", "basecolor", "roughness", "metallic", "emission")
 
@@ -219,7 +219,7 @@ def source_visibility(surface: Surface, report: SourceReport, points: torch.Tens
     return out
 
 
-MAX_LIGHT_SLOTS = 64                     # ESR_SURFACE_LIGHT_MAX_SLOTS: a source's sample slots sit in one wave
+MAX_LIGHT_SLOTS = _lib.SURFACE_LIGHT_MAX_SLOTS   # a source's sample slots sit in one wave
 
 
 @dataclass
@@ -344,7 +344,7 @@ def direct_light(surface: Surface, lights: SourceLights, points: torch.Tensor, n
     A sample is a point light standing for the area A = area_s / n_s; the clamp max(r^2, A) keeps it bounded, so within
     about one sample spacing of a source the estimate is LOW (far from it, it converges on the area integral).  ``bvh``: the
     ``raycast.Bvh`` of the surface, built here when None.  The same input gives the same bytes on every call; no read-back."""
-    from . import _lib, raycast
+    from . import raycast
     what = "direct_light"
     v = surface.vertices
     dev = v.device

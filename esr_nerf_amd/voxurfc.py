@@ -23,7 +23,7 @@ from .fine_engine import DX_ROWS, FineEngine, _Workspace, make_scene
 from .modules import DenseGrid, ForwardSwitch, Gaussian3DConv, GradientConv, MaskCache, _linears, _mlp_stack
 from .voxurff import VoxurfF
 
-KIND_COARSE = 4
+KIND_COARSE = _lib.MLP_COARSE
 XC_ROWS, HID = 72, 128
 
 

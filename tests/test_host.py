@@ -67,28 +67,112 @@ def test_a_bare_python_integer_reaches_an_int64_parameter_intact():
     assert L.esr_cd_hash_insert(p, 1 << 31, 1 << 32, p, None, None) == -2
 
 
-def test_ctypes_structs_match_the_c_layout():
-    """sizeof and every field's offsetof of every struct _lib mirrors, against the C compiler's (esr_bvh_node_t has no class:
-    tests/test_raycast_host.py pins its layout)."""
+def _lib_structs():
+    """typedef name -> class, by the inverse of _lib's naming rule (EsrFeatBwdSrc -> esr_feat_bwd_src_t)"""
     from esr_nerf_amd import _lib
-    structs = {re.sub(r"(?<!^)(?=[A-Z])", "_", c.__name__).lower() + "_t": c for c in vars(_lib).values()
-               if isinstance(c, type) and issubclass(c, ctypes.Structure) and c is not ctypes.Structure}
+    return {re.sub(r"(?<!^)(?=[A-Z])", "_", c.__name__).lower() + "_t": c for c in vars(_lib).values()
+            if isinstance(c, type) and issubclass(c, ctypes.Structure) and c is not ctypes.Structure}
+
+
+def test_ctypes_structs_match_the_c_layout():
+    """sizeof and every field's offsetof of every struct of the header, and the value of every integer #define, against the C
+    compiler's."""
+    from esr_nerf_amd import _lib
+    structs = _lib_structs()
     header = open(os.path.join(ROOT, "include", "esr_hip.h")).read()
-    assert set(structs) | {"esr_bvh_node_t"} == set(re.findall(r"^}\s*(esr_\w+_t)\s*;", header, re.M)) and len(structs) >= 21
+    assert set(structs) == set(re.findall(r"^}\s*(esr_\w+_t)\s*;", header, re.M)) and len(structs) >= 23
+    macros = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(ESR_\w+)[ \t]+\S", header, re.M)       # (ESR_HIP_H has no value)
+    assert len(macros) >= 30 and len(set(macros)) == len(macros)
     exprs = [e for t, c in structs.items() for e in [f"sizeof({t})"] + [f"offsetof({t},{f[0]})" for f in c._fields_]]
     src = ('#include <stdio.h>\n#include <stddef.h>\n#include "esr_hip.h"\nint main(){\n' +
-           "".join(f'printf("%zu\\n",{e});\n' for e in exprs) + "return 0;}\n")
+           "".join(f'printf("%zu\\n",{e});\n' for e in exprs) +
+           "".join(f'printf("%lld\\n",(long long)({m}));\n' for m in macros) + "return 0;}\n")
     with tempfile.TemporaryDirectory() as d:
         c = os.path.join(d, "t.c")
         open(c, "w").write(src)
         exe = os.path.join(d, "t")
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        got = dict(zip(exprs, (int(v) for v in subprocess.check_output([exe]).split())))
-    assert len(got) == len(exprs)
+        got = dict(zip(exprs + macros, (int(v) for v in subprocess.check_output([exe]).split())))
+    assert len(got) == len(exprs) + len(macros)
     for t, c in structs.items():
         assert got[f"sizeof({t})"] == ctypes.sizeof(c), t
         for f in c._fields_:
             assert got[f"offsetof({t},{f[0]})"] == getattr(c, f[0]).offset, (t, f[0])
+    for m in macros:
+        assert getattr(_lib, m[4:]) == got[m] and type(getattr(_lib, m[4:])) is int, m
+    assert got["ESR_EINVAL"] == -1 and got["ESR_ECAP"] == -2
+
+
+def _shape(ctype):
+    """(element ctype, array lengths outermost first) of a field's ctypes type"""
+    dims = []
+    while issubclass(ctype, ctypes.Array):
+        dims.append(ctype._length_)
+        ctype = ctype._type_
+    return ctype, dims
+
+
+# the test's own reading of the header's structs (not _lib's parser): typedef name -> the text between its braces
+STRUCT_BODIES = {t: body for body, t in re.findall(
+    r"typedef\s+struct[^{;]*\{([^{}]*)\}\s*(esr_\w+_t)\s*;",
+    re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "esr_hip.h")).read(), flags=re.S))}
+
+
+@pytest.mark.parametrize("typedef", sorted(STRUCT_BODIES))
+def test_every_struct_carries_the_fields_the_header_declares(typedef):
+    """Name, scalar / pointer / array, element type and array lengths of every field, in the header's order (offsets cannot tell
+    `int32_t a; float b;` from `float a; int32_t b;`): scalars as declared, every pointer a c_void_p except esr_march_t.scene."""
+    from esr_nerf_amd import _lib
+    header = open(os.path.join(ROOT, "include", "esr_hip.h")).read()
+    want = []
+    for decl in STRUCT_BODIES[typedef].split(";"):
+        words = decl.replace("const", " ").split(None, 1)
+        if not words:
+            continue
+        for d in words[1].split(","):
+            name = re.search(r"(\w+)\s*(?:\[|$)", d.strip()).group(1)
+            dims = [int(n) if n.isdigit() else int(re.search(rf"#define\s+{n}\s+(\d+)", header).group(1))
+                    for n in re.findall(r"\[\s*(\w+)\s*\]", d)]
+            want.append((name, ctypes.c_void_p if "*" in d else C_TYPES[words[0]], dims))
+    if typedef == "esr_march_t":
+        assert want[0] == ("scene", ctypes.c_void_p, [])
+        want[0] = ("scene", ctypes.POINTER(_lib.EsrScene), [])
+    assert len(want) >= 2
+    assert [(n, *_shape(t)) for n, t in _lib_structs()[typedef]._fields_] == want
+
+
+def test_struct_fields_are_the_ones_the_hand_written_classes_had():
+    """tests/golden/abi_struct_fields.json: names, order and types of the 22 classes _lib.py spelled out by hand before it
+    derived them from the header (EsrBvhNode had none: the two tests above cover it)."""
+    import json
+    names = {ctypes.c_int32: "int32", ctypes.c_int64: "int64", ctypes.c_float: "float", ctypes.c_double: "double",
+             ctypes.c_void_p: "void*"}
+
+    def type_name(t):
+        elem, dims = _shape(t)
+        base = f"POINTER({elem._type_.__name__})" if issubclass(elem, ctypes._Pointer) else names[elem]
+        return base + "".join(f"[{n}]" for n in dims)
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "abi_struct_fields.json")))
+    got = {c.__name__: [[n, type_name(t)] for n, t in c._fields_] for c in _lib_structs().values()}
+    assert len(golden) == 22 and set(got) == set(golden) | {"EsrBvhNode"}
+    for name, fields in golden.items():
+        assert got[name] == fields, name
+
+
+@pytest.mark.parametrize("text, offender", [
+    ("typedef struct esr_a { int32_t n; size_t bytes; } esr_a_t;", "bytes"),                  # a field type it does not know
+    ("typedef struct esr_a { int32_t n : 3; } esr_a_t;", "int32_t n : 3"),                    # a declaration it cannot consume
+    ("typedef struct esr_a { float v[ESR_NO_SUCH]; } esr_a_t;", "ESR_NO_SUCH"),               # a bound it has not read
+    ("typedef struct esr_a { union { float f; int32_t i; } u; } esr_a_t;", "struct esr_a"),   # a typedef it cannot match
+    ("struct esr_b;\ntypedef struct esr_a { float f; } esr_a_t;", "struct esr_b"),            # a struct no typedef accounts for
+    ("typedef struct esr_a { float f; } esr_a_t;\nint esr_f(const esr_a_t *a);", "esr_march_t"),   # typed-pointer keys that name
+])                                                                                                  # nothing in the header
+def test_header_parser_fails_loudly(tmp_path, text, offender):
+    from esr_nerf_amd import _lib
+    h = tmp_path / "esr_hip.h"
+    h.write_text("#define ESR_N 4\n" + text + "\n")
+    with pytest.raises(RuntimeError, match=re.escape(offender)):
+        _lib._parse_header(str(h))
 
 
 def _cpu_model(**model_over):
