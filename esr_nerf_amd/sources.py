@@ -18,7 +18,10 @@ fine.py:632) and knows emissive sources only per view, as the image masks ``any(
 ``source_lights``      the sources as area-weighted point lights at ``source_samples``' points, with edits applied
 ``direct_light``       their light at surface points, shadowed by the surface, reflected once by the light-transport stage's
                        Disney BRDF or as irradiance: one fused launch (csrc/surflight.hip, header section U)
-``lit_view``           the same for the pixels of a camera view
+``lit_view``           the same for the pixels of a camera view, with the environment's light on request
+``environment_light``  the light of the spherical-Gaussian environment map at surface points over a table of hemisphere
+                       directions (``hemisphere_directions``), shadowed by the surface, with one more bounce from a vertex
+                       radiance (``vertex_env_radiance``): one fused launch (csrc/surfenv.hip, header section V)
 
 Everything up to the file is device tensors; nothing here copies the mesh to the host.
 """
@@ -402,6 +405,146 @@ def direct_light(surface: Surface, lights: SourceLights, points: torch.Tensor, n
     return (out, seen) if return_seen else out
 
 
+MAX_ENV_DIRS = _lib.SURFACE_ENV_MAX_DIRS
+MAX_ENV_SG = _lib.SURFACE_ENV_MAX_SG
+
+
+def hemisphere_directions(n: int, device=None) -> torch.Tensor:
+    """float32 [n, 3]: the reference's ``fibonacci_spiral_samples_on_unit_hemisphere(n)`` (app/utils/pbr/functions.py:176-194
+    with ``random=False, up=True``), restated operation by operation on the host -- the upper half (z > 0) of a Fibonacci
+    spiral of 2 n points -- and copied to ``device``.  The mean of its z is exactly 1/2."""
+    n = int(n)
+    if n < 1 or n > MAX_ENV_DIRS:
+        raise ValueError(f"hemisphere_directions: 1 .. {MAX_ENV_DIRS} directions, got {n}")
+    m = 2 * n
+    rn = torch.arange(n, m)
+    ga = np.pi * (3.0 - np.sqrt(5.0))
+    phi = ga * ((rn + 1.0) % m)
+    cos_theta = ((rn + 0.5) * (1.0 / n)) - 1.0
+    sin_theta = torch.sqrt(1.0 - cos_theta * cos_theta)
+    out = torch.stack([torch.cos(phi) * sin_theta, torch.sin(phi) * sin_theta, cos_theta], dim=-1)
+    return out if device is None else out.to(device)
+
+
+def _env_parameters(what, env, dev):
+    """(mus [J, 3], lambdas [J], lobes [J, 3]) float32 on ``dev`` of a SphericalGaussian or of a (mus, lambdas, lobes) tuple"""
+    if isinstance(env, (tuple, list)):
+        if len(env) != 3:
+            raise ValueError(f"{what}: env is a SphericalGaussian or a (mus, lambdas, lobes) tuple")
+        mus, lambdas, lobes = env
+    elif all(hasattr(env, k) for k in ("mus", "lambdas", "lobes")):
+        mus, lambdas, lobes = env.mus, env.lambdas, env.lobes
+    else:
+        raise ValueError(f"{what}: env is a SphericalGaussian or a (mus, lambdas, lobes) tuple")
+    for name, x in (("mus", mus), ("lambdas", lambdas), ("lobes", lobes)):
+        if not isinstance(x, torch.Tensor) or x.device != dev or x.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"{what}: env.{name} must be a float tensor on the surface's device")
+    J = int(mus.shape[0]) if mus.dim() == 2 else -1
+    if J < 1 or J > MAX_ENV_SG or tuple(mus.shape) != (J, 3) or tuple(lobes.shape) != (J, 3) or lambdas.numel() != J:
+        raise ValueError(f"{what}: env holds 1 .. {MAX_ENV_SG} lobes: mus [J, 3], lambdas [J] or [J, 1], lobes [J, 3]")
+    return tuple(x.detach().float().contiguous() for x in (mus, lambdas.reshape(J), lobes))
+
+
+def _env_dirs(what, dirs, dev):
+    if isinstance(dirs, torch.Tensor):
+        R = int(dirs.shape[0]) if dirs.dim() == 2 else -1
+        if dirs.device != dev or dirs.dtype not in (torch.float32, torch.float64) or R < 1 or tuple(dirs.shape) != (R, 3):
+            raise ValueError(f"{what}: dirs is a count or a float [R, 3] tensor of unit directions on the surface's device")
+        if R > MAX_ENV_DIRS:
+            raise ValueError(f"{what}: at most {MAX_ENV_DIRS} directions, got {R}")
+        return dirs.float().contiguous()
+    if isinstance(dirs, bool) or not isinstance(dirs, int) or not 1 <= dirs <= MAX_ENV_DIRS:
+        raise ValueError(f"{what}: dirs is a count in 1 .. {MAX_ENV_DIRS} or a float [R, 3] tensor, got {dirs!r}")
+    return hemisphere_directions(dirs, dev)
+
+
+@torch.no_grad()
+def environment_light(surface: Surface, env, points: torch.Tensor, normals: torch.Tensor, basecolor=None, roughness=None,
+                      metallic=None, wo=None, dirs=128, faces=None, vertex_radiance=None, bvh=None, t_min: float = 1e-6,
+                      return_open: bool = False, return_hit: bool = False):
+    """The light of the environment map ``env`` at the surface points ``points`` [P, 3] with the unit shading normals
+    ``normals`` [P, 3], in one fused launch (``esr_surface_env``, section V of include/esr_hip.h): per point the R directions
+    of one table (``dirs``: a count, then ``hemisphere_directions``, or a float [R, 3] tensor) are flipped into the normal's
+    hemisphere as the reference's ``diffuse_scattering_fib`` flips them, cast against the surface from ``t_min`` on (the face
+    ``faces`` [P] int32 of each point never hit; -1: none), and the incoming radiance -- the environment where the ray leaves
+    the mesh; where it hits, 0 or with ``vertex_radiance`` float32 [V, 3] that radiance interpolated on the nearest face -- is
+
+    with ``wo`` [P, 3] (unit, towards the viewer), ``basecolor`` [P, 3], ``roughness`` [P] and ``metallic`` [P]: reflected
+    towards ``wo`` by the Disney BRDF of the light-transport stage, the mean over the directions (the reference's
+    ``lin/env_dir``, with ``vertex_radiance`` plus its ``lin/env_indir``);
+    with ``wo=None``: the irradiance, 2 pi times the mean of L cos.
+
+    ``env`` is the model's ``SphericalGaussian`` or a ``(mus, lambdas, lobes)`` tuple of its raw parameters: an environment
+    is edited by passing rotated lobes or scaled mus.  -> float32 [P, 3]; ``return_open`` adds float32 [P], the share of
+    directions that leave the mesh (n_open / R); ``return_hit`` adds uint8 [P, R].  ``bvh``: the ``raycast.Bvh`` of the
+    surface, built here when None.  One table of directions serves all points.  The same input gives the same bytes on every
+    call; no read-back."""
+    from . import raycast
+    what = "environment_light"
+    v = surface.vertices
+    dev = v.device
+    mus, lambdas, lobes = _env_parameters(what, env, dev)
+    table = _env_dirs(what, dirs, dev)
+    R = int(table.shape[0])
+    if not isinstance(points, torch.Tensor) or points.dim() != 2:
+        raise ValueError(f"{what}: points must be a float [P, 3] tensor on the surface's device")
+    P = int(points.shape[0])
+    _light_input(what, "points", points, (P, 3), dev)
+    _light_input(what, "normals", normals, (P, 3), dev)
+    if P >= 2 ** 31:
+        raise ValueError(f"{what}: {P} points exceed the kernel's 31-bit count")
+    if not float(t_min) >= 0.0:
+        raise ValueError(f"{what}: t_min is not negative, got {t_min}")
+    if faces is not None:
+        _light_input(what, "faces", faces, (P,), dev, dtypes=(torch.int32,))
+    V = int(v.shape[0])
+    if vertex_radiance is not None:
+        _light_input(what, "vertex_radiance", vertex_radiance, (V, 3), dev)
+    mode = 1 if wo is None else 0
+    mat = [None] * 4
+    if mode == 0:
+        if basecolor is None or roughness is None or metallic is None:
+            raise ValueError(f"{what}: with wo the reflection needs basecolor, roughness and metallic")
+        mat = [_light_input(what, name, x, shape, dev).float().contiguous()
+               for name, x, shape in (("basecolor", basecolor, (P, 3)), ("roughness", roughness, (P,)), ("metallic", metallic, (P,)),
+                                      ("wo", wo, (P, 3)))]
+    if bvh is None:
+        bvh = raycast.build(v, surface.triangles)
+    elif not isinstance(bvh, raycast.Bvh) or bvh.vertices.device != dev:
+        raise ValueError(f"{what}: bvh is the raycast.Bvh of the surface")
+    out = torch.zeros(P, 3, dtype=torch.float32, device=dev)
+    n_open = torch.zeros(P, dtype=torch.int32, device=dev) if return_open else None
+    hit = torch.zeros(P, R, dtype=torch.uint8, device=dev) if return_hit else None
+    if P:
+        pts, nrm = points.double().contiguous(), normals.float().contiguous()
+        rad = None if vertex_radiance is None else vertex_radiance.float().contiguous()
+        fc = None if faces is None else faces.contiguous()
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().esr_surface_env(
+                _lib.ptr(bvh.nodes), bvh.n_faces, _lib.ptr(bvh.vertices), int(bvh.vertices.shape[0]), _lib.ptr(bvh.triangles),
+                _lib.ptr(table), R, _lib.ptr(mus), _lib.ptr(lambdas), _lib.ptr(lobes), int(mus.shape[0]), _lib.ptr(rad), P,
+                _lib.ptr(pts), _lib.ptr(nrm), _lib.ptr(fc), _lib.ptr(mat[0]), _lib.ptr(mat[1]), _lib.ptr(mat[2]), _lib.ptr(mat[3]),
+                mode, float(t_min), _lib.ptr(out), _lib.ptr(n_open), _lib.ptr(hit), _lib.stream_ptr(dev)), "esr_surface_env")
+    res = (out,)
+    if return_open:
+        res += (n_open.float() / float(R),)
+    if return_hit:
+        res += (hit,)
+    return res if len(res) > 1 else out
+
+
+@torch.no_grad()
+def vertex_env_radiance(surface: Surface, env, dirs=128, bvh=None) -> torch.Tensor:
+    """float32 [V, 3]: ``environment_light`` at every vertex with the vertex's own normal (normalised again) and material and
+    ``wo`` = that normal -- the view-independent first bounce of the environment's light, for baking and as the
+    ``vertex_radiance`` of a second gather."""
+    a = surface.attrs
+    n = a["normal"].float()
+    n = n / torch.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2]).clamp(min=1e-12)[:, None]
+    return environment_light(surface, env, surface.vertices, n, a["basecolor"].float().reshape(-1, 3), a["roughness"].float().reshape(-1),
+                             a["metallic"].float().reshape(-1), n, dirs=dirs, bvh=bvh)
+
+
 def _hit_points(surface: Surface, hit, d):
     """What ``lit_view`` knows at the nearest hits ``hit`` (``raycast.Hits``) of the rays with the directions ``d``: the point
     (float64, NaN where the ray misses: such a point is lit by nothing), the unit shading normal, the interpolated
@@ -425,7 +568,8 @@ def _hit_points(surface: Surface, hit, d):
 
 
 @torch.no_grad()
-def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: int = 16, edits=None, bvh=None):
+def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: int = 16, edits=None, bvh=None, env=None,
+             env_dirs=128, bounces: int = 0):
     """View ``view`` of ``cams`` lit by the (edited) sources, without an optimiser step: the nearest face of every pixel
     (the rays and the walk of ``raycast.cast_cameras``), the vertex attributes interpolated with the hit's barycentrics in
     torch (the normal normalised again), ``wo`` = minus the unit pixel ray, and ``direct_light`` with ``source_lights(surface,
@@ -436,9 +580,21 @@ def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: i
     ``face``        int32 [H, W]       as ``cast_cameras``; -1 where the ray misses
     ``depth``       float64 [H, W]     as ``cast_cameras``; +inf where the ray misses
 
-    A pixel that misses is 0 in both images.  The linear image of the edited scene is ``off + lin/emit + lin/reflect``
-    where ``off`` -- the light of the environment, which no source edit changes -- stays the volumetric renderer's.  The
-    near-field limit of ``direct_light`` applies.  Nothing is read back."""
+    With ``env`` (the model's ``SphericalGaussian`` or a ``(mus, lambdas, lobes)`` tuple, as ``environment_light`` takes it)
+    the light of the environment is added, over the ``env_dirs`` hemisphere directions (a count or a [R, 3] table):
+
+    ``lin/env_dir``   float32 [H, W, 3]  the environment's light that reaches the pixel's point directly, reflected towards
+                                         the camera (the reference's ``lin/env_dir`` on the surface)
+    ``etc/open``      float32 [H, W]     the share of the point's directions that leave the mesh
+    ``lin/env_indir`` float32 [H, W, 3]  only with ``bounces == 1``: the environment's light that reaches the point by way of
+                                         one other surface point -- a second launch whose rays take ``vertex_env_radiance``
+                                         from the face they hit, minus ``lin/env_dir``
+
+    With ``env=None`` the keys and their bytes are those above and nothing else.  A pixel that misses is 0 in every image.
+    The linear image of the edited scene is ``lin/emit + lin/reflect + lin/env_dir (+ lin/env_indir)``.  Limits: one table
+    of directions for all points (no per-point random rotation), one extra bounce at the most, and that bounce is
+    view-independent (the radiance a vertex sends along its own normal stands for every direction).  The near-field limit of
+    ``direct_light`` applies.  Nothing is read back."""
     from . import raycast
     from .relight import edit_emission
     what = "lit_view"
@@ -452,6 +608,11 @@ def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: i
     if cams.device != dev:
         raise ValueError(f"{what}: the surface and the cameras are on one device")
     tables = _edit_tables(what, S, edits, dev) if edits else None
+    if env is not None:
+        if isinstance(bounces, bool) or bounces not in (0, 1):
+            raise ValueError(f"{what}: bounces is 0 or 1, got {bounces!r}")
+        env = _env_parameters(what, env, dev)
+        env_dirs = _env_dirs(what, env_dirs, dev)
     if bvh is None:
         bvh = raycast.build(v, t)
     lights = source_lights(surface, report, samples, edits)
@@ -460,7 +621,12 @@ def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: i
     hit = raycast.cast(bvh, o, d)
     if not t.shape[0]:                                                     # (no face: every ray misses)
         black = torch.zeros(H, W, 3, dtype=torch.float32, device=dev)
-        return {"lin/reflect": black, "lin/emit": black.clone(), "face": hit.face.reshape(H, W), "depth": hit.t.reshape(H, W)}
+        res = {"lin/reflect": black, "lin/emit": black.clone(), "face": hit.face.reshape(H, W), "depth": hit.t.reshape(H, W)}
+        if env is not None:
+            res["lin/env_dir"], res["etc/open"] = black.clone(), torch.zeros(H, W, dtype=torch.float32, device=dev)
+            if bounces:
+                res["lin/env_indir"] = black.clone()
+        return res
     got = hit.face >= 0
     x, normal, a, wo = _hit_points(surface, hit, d)
     reflect = direct_light(surface, lights, x, normal, a["basecolor"], a["roughness"][:, 0], a["metallic"][:, 0], wo, bvh=bvh)
@@ -471,9 +637,19 @@ def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: i
         sid = src.clamp(min=0).long()
         emit = edit_emission(emit, tables[0][sid].contiguous(), tables[1][sid].contiguous(), tables[2][sid].contiguous())
     zero = torch.zeros(1, 3, dtype=torch.float32, device=dev)
-    return {"lin/reflect": torch.where(got[:, None], reflect, zero).reshape(H, W, 3),
-            "lin/emit": torch.where(lit[:, None], emit, zero).reshape(H, W, 3),
-            "face": hit.face.reshape(H, W), "depth": hit.t.reshape(H, W)}
+    res = {"lin/reflect": torch.where(got[:, None], reflect, zero).reshape(H, W, 3),
+           "lin/emit": torch.where(lit[:, None], emit, zero).reshape(H, W, 3),
+           "face": hit.face.reshape(H, W), "depth": hit.t.reshape(H, W)}
+    if env is not None:
+        at = (x, normal, a["basecolor"], a["roughness"][:, 0], a["metallic"][:, 0], wo)
+        direct, share = environment_light(surface, env, *at, dirs=env_dirs, faces=hit.face, bvh=bvh, return_open=True)
+        res["lin/env_dir"] = torch.where(got[:, None], direct, zero).reshape(H, W, 3)
+        res["etc/open"] = torch.where(got, share, zero[0, 0]).reshape(H, W)
+        if bounces:
+            both = environment_light(surface, env, *at, dirs=env_dirs, faces=hit.face, bvh=bvh,
+                                     vertex_radiance=vertex_env_radiance(surface, env, env_dirs, bvh=bvh))
+            res["lin/env_indir"] = torch.where(got[:, None], both - direct, zero).reshape(H, W, 3)
+    return res
 
 
 VERTEX_PROPERTIES = ["x", "y", "z", "nx", "ny", "nz", "basecolor_r", "basecolor_g", "basecolor_b", "roughness", "metallic",
@@ -517,4 +693,5 @@ def write_surface_ply(path, surface: Surface, face_source: Optional[torch.Tensor
 
 
 __all__ = ["Surface", "SourceReport", "extract_surface", "emissive_sources", "simplify_surface", "write_surface_ply",
-           "source_samples", "source_visibility", "SourceLights", "source_lights", "direct_light", "lit_view", "VERTEX_PROPERTIES"]
+           "source_samples", "source_visibility", "SourceLights", "source_lights", "direct_light", "lit_view", "VERTEX_PROPERTIES",
+           "hemisphere_directions", "environment_light", "vertex_env_radiance"]

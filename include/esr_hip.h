@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 44
+#define ESR_ABI_VERSION 45
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -1832,6 +1832,73 @@ typedef struct esr_surface_light {
 } esr_surface_light_t;
 
 int esr_surface_light(const esr_surface_light_t *args, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * V. Environment light on the surface (esr_nerf_amd/sources.py: environment_light, vertex_env_radiance, lit_view): the
+ *    light of the spherical-Gaussian environment map that reaches a surface point -- directly where the hemisphere ray
+ *    leaves the mesh, or once reflected where it hits a face with a known vertex radiance -- reflected by the Disney BRDF
+ *    of the light-transport stage or as irradiance.  The reference's evaluation decomposition defines the quantity in the
+ *    volume (app/fine/model/esrnerf.py:983-994: lin/env_dir = mean_r(envmap(dirs_r) alphainv_last_r R_r), lin/env_indir =
+ *    mean_r(off_marched_r R_r) over the directions of diffuse_scattering_fib, app/utils/pbr/functions.py:21-32, 176-194);
+ *    on a surface alphainv_last is "the ray leaves the mesh" and off_marched the radiance of the face that is hit
+ * ------------------------------------------------------------------------- */
+
+#define ESR_SURFACE_ENV_MAX_DIRS 4096    /* most directions of the table (ESR_ECAP beyond it) */
+#define ESR_SURFACE_ENV_MAX_SG   64      /* most lobes of the environment (ESR_ECAP beyond it: the lobe table sits in LDS) */
+
+/*
+ * Scene.  nodes / n_faces / vertices / n_vertices / triangles: the tree and the mesh exactly as esr_bvh_cast takes them (the
+ * same pointer and alignment rules; n_faces == 0 makes every ray a miss, n_faces == 1 is the tree-less case).
+ * Directions.  dirs f32 [R,3], R = n_dirs unit directions: one table for all points.
+ * Environment.  The raw model parameters mus f32 [J,3], lambdas f32 [J], lobes f32 [J,3], J = n_sg.
+ * vertex_radiance f32 [n_vertices,3] or NULL: the radiance that leaves the surface at every vertex.
+ * Points.  n_points points (P): p_point f64 [P,3], p_normal f32 [P,3] (unit length), p_face i32 [P] or NULL (the face the
+ * point lies on, which its rays never hit; -1: none); in mode 0 also p_base f32 [P,3], p_rough f32 [P], p_metal f32 [P] and
+ * p_wo f32 [P,3], the unit direction towards the viewer (unused and may be NULL in mode 1).
+ *
+ * Per point x with normal n, and per direction r with the table entry w = dirs[r]:
+ *   1. flip (as diffuse_scattering_fib): s = (w0 n0 + w1 n1) + w2 n2 in binary32, every operation rounded on its own (no
+ *      contraction); if s < 0 then w = -w.
+ *   2. ray: o = x, d = (double)w, t_min < t <= +inf, skip_face = p_face[p].  The walk and the triangle test are
+ *      esr_bvh_cast's: the any-hit walk if vertex_radiance is NULL, the nearest-hit walk otherwise.  (A point with a
+ *      component that is not finite hits nothing: all its rays miss.)
+ *   3. incoming radiance L.
+ *      miss: the environment, binary32, every operation rounded on its own, in the order of the light-transport combine:
+ *        l^_j = lobe_j / max(sqrt((lobe_j0^2 + lobe_j1^2) + lobe_j2^2), 1e-12)
+ *        pre_c = sum over j ascending of mu_jc expf(|lambda_j| (((w0 l^_j0 + w1 l^_j1) + w2 l^_j2) - 1))
+ *        L_c = softplus(pre_c) = pre_c > 20 ? pre_c : log1pf(expf(pre_c)), with the flipped w
+ *      hit with vertex_radiance: binary64, every operation rounded on its own, with the hit's barycentrics u, v and the rows
+ *        E_a, E_b, E_c of the face's three vertices:  L_c = (((1 - u) - v) E_a,c + u E_b,c) + v E_c,c
+ *      hit without vertex_radiance: L = 0.
+ *   4. term.
+ *      mode 0 (reflected radiance)  term_c = (double)L_c (double)R_c,  R = the binary32 Disney reflection of the
+ *             light-transport combine for base, rough, metal, n, wi = w, wo: it carries (n . wi) 2 pi, the weight of the
+ *             uniform-hemisphere estimator
+ *      mode 1 (irradiance)          term_c = (double)L_c cos_x,  cos_x = (n0 w0 + n1 w1) + n2 w2 in binary64 on the widened
+ *             values
+ *   5. sum, in a fixed order without atomics (the same input gives the same bytes on every call).  Kd = min(64, the next
+ *      power of two >= R) adjacent lanes form the group of a point; lane k adds the terms of its directions r = k, k + Kd,
+ *      ... ascending in binary64 (from +0.0); the Kd lane sums are combined by the balanced pairwise sum of section U (lanes
+ *      2 j and 2 j + 1 first, then adjacent pairs of those sums, and so on) to S_c.
+ *        mode 0:  out[p,c] = (float)(S_c / (double)R)
+ *        mode 1:  out[p,c] = (float)((S_c (2 pi)) / (double)R), 2 pi from pi rounded to binary64
+ * out f32 [P,3]; n_open i32 [P] or NULL: the exact number of directions that miss; hit u8 [P,R] or NULL: 1 where the
+ * direction hits a face, else 0.
+ *
+ * n_points == 0 (with every other argument valid) succeeds and touches no pointer.  ESR_EINVAL: a negative size, n_dirs <
+ * 1, n_sg < 1, a mode other than 0 and 1, t_min negative or NaN, a NULL or misaligned required pointer (f64 / i64: 8
+ * bytes, nodes: 16, the rest: 4; an optional pointer that is given is held to the same alignment).  ESR_ECAP: n_dirs >
+ * ESR_SURFACE_ENV_MAX_DIRS, n_sg > ESR_SURFACE_ENV_MAX_SG, a size >= 2^31.  Nothing is launched in either case.  One
+ * launch on `stream`; nothing waits on the host.
+ * Layout: a wave holds 64 / Kd points; the point stays in registers over the directions; the environment is evaluated only
+ * on the lanes whose ray missed; the lobe table sits in LDS; nothing of size P R reaches memory but `hit`.
+ */
+int esr_surface_env(const esr_bvh_node_t *nodes, int64_t n_faces, const double *vertices, int64_t n_vertices,
+                    const int64_t *triangles, const float *dirs, int32_t n_dirs, const float *mus, const float *lambdas,
+                    const float *lobes, int32_t n_sg, const float *vertex_radiance, int64_t n_points, const double *p_point,
+                    const float *p_normal, const int32_t *p_face, const float *p_base, const float *p_rough,
+                    const float *p_metal, const float *p_wo, int32_t mode, double t_min, float *out, int32_t *n_open,
+                    uint8_t *hit, void *stream);
 
 #ifdef __cplusplus
 }
