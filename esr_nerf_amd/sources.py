@@ -23,10 +23,18 @@ fine.py:632) and knows emissive sources only per view, as the image masks ``any(
                        directions (``hemisphere_directions``), shadowed by the surface, with one more bounce from a vertex
                        radiance (``vertex_env_radiance``): one fused launch (csrc/surfenv.hip, header section V)
 
+``bake_materials``     the materials at the texel centres of a texture atlas (``atlas.build``; csrc/atlas.hip, header section
+                       W): queried from the model at every owned texel's point, or interpolated from the vertices
+``bake_irradiance``    ``direct_light`` per source and ``environment_light`` as irradiance at the texels inside their faces
+``write_surface_obj``  OBJ + MTL with the baked maps as 8-bit PNGs (emission also as Radiance .hdr and .npy)
+
 Everything up to the file is device tensors; nothing here copies the mesh to the host.
 """
 from __future__ import annotations
 
+import os
+import struct
+import zlib
 from dataclasses import dataclass
 from typing import Dict, Optional
 
@@ -569,7 +577,7 @@ def _hit_points(surface: Surface, hit, d):
 
 @torch.no_grad()
 def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: int = 16, edits=None, bvh=None, env=None,
-             env_dirs=128, bounces: int = 0):
+             env_dirs=128, bounces: int = 0, atlas=None, textures=None):
     """View ``view`` of ``cams`` lit by the (edited) sources, without an optimiser step: the nearest face of every pixel
     (the rays and the walk of ``raycast.cast_cameras``), the vertex attributes interpolated with the hit's barycentrics in
     torch (the normal normalised again), ``wo`` = minus the unit pixel ray, and ``direct_light`` with ``source_lights(surface,
@@ -594,10 +602,19 @@ def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: i
     The linear image of the edited scene is ``lin/emit + lin/reflect + lin/env_dir (+ lin/env_indir)``.  Limits: one table
     of directions for all points (no per-point random rotation), one extra bounce at the most, and that bounce is
     view-independent (the radiance a vertex sends along its own normal stands for every direction).  The near-field limit of
-    ``direct_light`` applies.  Nothing is read back."""
+    ``direct_light`` applies.  Nothing is read back.
+
+    With ``atlas`` and ``textures`` (``atlas.build`` of this surface and the dict of ``bake_materials``; both or neither) the
+    basecolor, roughness, metallic, emission and the shading normal of every pixel are looked up in the textures
+    (``atlas.sample`` at the hit's face and barycentrics; the normal normalised again) instead of interpolated from the
+    vertices; ``face`` and ``depth`` are unchanged.  With None the keys and bytes are those of the vertex path."""
     from . import raycast
     from .relight import edit_emission
     what = "lit_view"
+    if (atlas is None) != (textures is None):
+        raise ValueError(f"{what}: atlas and textures come together")
+    if textures is not None and any(k not in textures for k in TEXTURE_KEYS):
+        raise ValueError(f"{what}: textures holds {TEXTURE_KEYS}")
     if isinstance(view, bool) or not isinstance(view, int) or not 0 <= view < cams.n_views:
         raise ValueError(f"{what}: view {view!r} of a set of {cams.n_views}")
     samples = int(samples)
@@ -629,6 +646,8 @@ def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: i
         return res
     got = hit.face >= 0
     x, normal, a, wo = _hit_points(surface, hit, d)
+    if atlas is not None:
+        normal, a = _hit_textures(what, surface, atlas, textures, hit)
     reflect = direct_light(surface, lights, x, normal, a["basecolor"], a["roughness"][:, 0], a["metallic"][:, 0], wo, bvh=bvh)
     src = report.face_source[hit.face.clamp(min=0).long()]
     lit = got & (src >= 0)
@@ -650,6 +669,215 @@ def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: i
                                      vertex_radiance=vertex_env_radiance(surface, env, env_dirs, bvh=bvh))
             res["lin/env_indir"] = torch.where(got[:, None], both - direct, zero).reshape(H, W, 3)
     return res
+
+
+TEXTURE_KEYS = ("normal", "basecolor", "roughness", "metallic", "emission")
+
+
+def _hit_textures(what, surface, atlas, textures, hit):
+    """the unit shading normal and the material dict of ``_hit_points`` from the textures: one ``atlas.sample`` of the 11
+    channels at the hits"""
+    from . import atlas as _atlas
+    if int(atlas.uv.shape[0]) != int(surface.triangles.shape[0]):
+        raise ValueError(f"{what}: the atlas was built from another surface")
+    W = atlas.size
+    packed = torch.cat([textures[k].float().reshape(W, W, -1) for k in TEXTURE_KEYS], dim=2).contiguous()
+    got = _atlas.sample(atlas, packed, hit.face, hit.bary)
+    a, at = {}, 0
+    for k in TEXTURE_KEYS:
+        a[k] = got[:, at:at + _ATTR_WIDTH[k]].contiguous()
+        at += _ATTR_WIDTH[k]
+    n = a["normal"]
+    n = n / torch.sqrt((n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2]).clamp(min=1e-12)[:, None]
+    return n, a
+
+
+def _check_atlas(what, surface, atlas):
+    from .atlas import Atlas
+    if not isinstance(atlas, Atlas) or atlas.face is None or atlas.face.device != surface.vertices.device or \
+            int(atlas.uv.shape[0]) != int(surface.triangles.shape[0]):
+        raise ValueError(f"{what}: atlas is the atlas.build of this surface")
+
+
+@torch.no_grad()
+def bake_materials(surface: Surface, atlas, model=None, chunk: int = 1 << 18) -> Dict[str, torch.Tensor]:
+    """The materials at the texel centres of ``atlas`` (``atlas.build(surface.vertices, surface.triangles, ...)``) -> dict of
+    device float32 textures for ``ATTR_KEYS``: ``normal``, ``basecolor``, ``emission`` [W, W, 3], ``sdf``, ``roughness``,
+    ``metallic`` [W, W]; 0 where a texel belongs to no face.
+
+    With ``model``: ``surface_attributes`` at the world point of every owned texel (gutter texels included: their points lie
+    on the face's plane just outside it), the points clamped to the model's box as ``extract_surface`` clamps them.  The
+    detail is the model's, not the mesh's.  Without: the vertex attributes interpolated (in the gutter, extrapolated) by the
+    texel pass itself, all 12 channels in one launch; normals are not normalised again (``lit_view`` does that per pixel)."""
+    from . import atlas as _atlas
+    what = "bake_materials"
+    _check_atlas(what, surface, atlas)
+    W, dev = atlas.size, surface.vertices.device
+    if model is None:
+        packed = torch.cat([surface.attrs[k].reshape(surface.vertices.shape[0], -1).float() for k in ATTR_KEYS], dim=1).contiguous()
+        tex = _atlas.texels(atlas, surface.vertices, surface.triangles, packed)[4]
+        out, at = {}, 0
+        for k in ATTR_KEYS:
+            w = _ATTR_WIDTH[k]
+            out[k] = (tex[:, :, at:at + w] if surface.attrs[k].dim() == 2 else tex[:, :, at]).contiguous()
+            at += w
+        return out
+    own = (atlas.face >= 0).reshape(-1)
+    idx = torch.nonzero(own).reshape(-1)
+    lo, hi = (b.to(dev) for b in mesh._box(model))
+    pts = torch.minimum(torch.maximum(atlas.point.reshape(-1, 3)[idx], lo), hi)
+    got = model.surface_attributes(pts, chunk=chunk) if idx.numel() else None
+    out = {}
+    for k in ATTR_KEYS:
+        w = _ATTR_WIDTH[k]
+        flat = torch.zeros(W * W, w, dtype=torch.float32, device=dev)
+        if got is not None:
+            flat[idx] = got[k].reshape(-1, w).float()
+        out[k] = flat.reshape(W, W, w) if k in ("normal", "basecolor", "emission") else flat.reshape(W, W)
+    return out
+
+
+@torch.no_grad()
+def bake_irradiance(surface: Surface, atlas, report: SourceReport, samples: int = 16, edits=None, env=None, env_dirs=128, bvh=None,
+                    chunk: int = 1 << 18) -> Dict[str, torch.Tensor]:
+    """The irradiance at the texels of ``atlas`` whose centre lies inside their face, with the face's geometric unit normal:
+
+    ``light/sources`` float32 [W, W, S, 3]  ``direct_light(per_source=True)`` without ``wo``: per source, so that an intensity
+                                            edit stays a re-weighting of the texture
+    ``light/env``     float32 [W, W, 3]     only with ``env``: ``environment_light`` without ``wo`` over ``env_dirs``, the
+                                            texel's own face skipped as ``lit_view`` skips the hit face
+
+    0 at every other texel.  ``chunk`` texels per launch."""
+    from . import raycast
+    what = "bake_irradiance"
+    _check_atlas(what, surface, atlas)
+    v, t = surface.vertices, surface.triangles
+    W, dev, S = atlas.size, v.device, len(report)
+    if bvh is None:
+        bvh = raycast.build(v, t)
+    lights = source_lights(surface, report, samples, edits)
+    if env is not None:
+        env = _env_parameters(what, env, dev)
+        env_dirs = _env_dirs(what, env_dirs, dev)
+    idx = torch.nonzero(((atlas.flags & 1) != 0).reshape(-1)).reshape(-1)
+    face = atlas.face.reshape(-1)[idx].contiguous()
+    pts = atlas.point.reshape(-1, 3)[idx].double()
+    nrm = face_normals(surface)[face.long()]
+    src = torch.zeros(W * W, S, 3, dtype=torch.float32, device=dev)
+    out = {"light/sources": src}
+    if env is not None:
+        out["light/env"] = torch.zeros(W * W, 3, dtype=torch.float32, device=dev)
+    step = max(1, int(chunk))
+    for c0 in range(0, int(idx.shape[0]), step):
+        sl = slice(c0, c0 + step)
+        src[idx[sl]] = direct_light(surface, lights, pts[sl], nrm[sl], bvh=bvh, per_source=True)
+        if env is not None:
+            out["light/env"][idx[sl]] = environment_light(surface, env, pts[sl], nrm[sl], dirs=env_dirs, faces=face[sl].contiguous(),
+                                                          bvh=bvh)
+    out["light/sources"] = src.reshape(W, W, S, 3)
+    if env is not None:
+        out["light/env"] = out["light/env"].reshape(W, W, 3)
+    return out
+
+
+def face_normals(surface: Surface) -> torch.Tensor:
+    """float32 [F, 3]: the unit normal n / |n|, n = (b - a) x (c - a), of every face (float64, every operation its own launch,
+    as ``source_lights``; a degenerate face gets 0)"""
+    v, t = surface.vertices, surface.triangles
+    a, b, c = (v[t[:, k]] for k in range(3))
+    e1, e2 = b - a, c - a
+    n0 = e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1]
+    n1 = e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2]
+    n2 = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+    length = torch.sqrt((n0 * n0 + n1 * n1) + n2 * n2)
+    n = torch.stack([n0, n1, n2], -1) / length[:, None]
+    return torch.where(torch.isfinite(n).all(dim=1, keepdim=True), n, torch.zeros_like(n)).float()
+
+
+def quantise8(x: np.ndarray) -> np.ndarray:
+    """uint8: x clamped to [0, 1] (NaN -> 0), times 255, rounded half to even"""
+    x = np.nan_to_num(np.asarray(x, dtype=np.float64), nan=0.0)
+    return np.rint(np.clip(x, 0.0, 1.0) * 255.0).astype(np.uint8)
+
+
+def png_bytes(image: np.ndarray) -> bytes:
+    """an 8-bit PNG (grey for [H, W] or [H, W, 1], RGB for [H, W, 3]) of a uint8 array: zlib and struct, no imaging package;
+    filter 0 on every row"""
+    img = np.asarray(image)
+    if img.dtype != np.uint8 or img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] not in (1, 3)) or img.size == 0:
+        raise ValueError("png_bytes: a uint8 [H, W], [H, W, 1] or [H, W, 3] array")
+    h, w = img.shape[:2]
+    c = 1 if img.ndim == 2 else img.shape[2]
+    rows = np.concatenate([np.zeros((h, 1), np.uint8), img.reshape(h, w * c)], axis=1)
+
+    def chunk(kind, body):
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xffffffff)
+    head = struct.pack(">IIBBBBB", w, h, 8, 2 if c == 3 else 0, 0, 0, 0)
+    return b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", head) + chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b"")
+
+
+def hdr_bytes(image: np.ndarray) -> bytes:
+    """a flat (not run-length encoded) Radiance RGBE picture of a float [H, W, 3] array; negative and NaN values are 0"""
+    img = np.nan_to_num(np.asarray(image, dtype=np.float64), nan=0.0, posinf=3e38)
+    if img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("hdr_bytes: a float [H, W, 3] array")
+    img = np.clip(img, 0.0, None)
+    h, w = img.shape[:2]
+    top = img.max(axis=2)
+    mant, expo = np.frexp(top)                                          # top = mant 2^expo, mant in [0.5, 1)
+    live = top > 1e-32
+    scale = np.where(live, np.ldexp(1.0, 8 - expo), 0.0)                 # 256 / 2^expo
+    px = np.zeros((h, w, 4), np.uint8)
+    px[..., :3] = np.minimum(np.floor(img * scale[..., None]), 255).astype(np.uint8)
+    px[..., 3] = np.where(live, np.clip(expo + 128, 0, 255), 0).astype(np.uint8)
+    return b"#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n" + f"-Y {h} +X {w}\n".encode("ascii") + px.tobytes()
+
+
+def write_surface_obj(path, surface: Surface, atlas, textures, gamma=None):
+    """The surface as ``path`` (an .obj) with its baked maps beside it -> the list of the files written.
+
+    OBJ: ``v`` (repr of the float64 coordinates), three ``vt`` per face (u = x / W, v = 1 - y / W: image row 0 is the top)
+    and ``f v/vt``, 1-based.  MTL (same stem): ``map_Kd`` basecolor, ``map_Pr`` roughness, ``map_Pm`` metallic, ``map_Ke``
+    emission, ``norm`` the normal as n / 2 + 1 / 2.  The maps are 8-bit PNGs (``png_bytes``), clamped to [0, 1] and rounded
+    half to even; basecolor goes through ``gamma`` first (default ``metrics.apply_gamma_curve``), the others are linear.
+    Emission exceeds 1, so it is also written as a flat Radiance ``_emission.hdr`` and as ``_emission.npy`` (float32)."""
+    _need = [k for k in TEXTURE_KEYS if k not in textures]
+    if _need:
+        raise ValueError(f"write_surface_obj: textures lacks {_need}")
+    W = atlas.size
+    stem = os.path.splitext(str(path))[0]
+    name = os.path.basename(stem)
+    v = np.asarray(surface.vertices.detach().cpu(), dtype=np.float64).reshape(-1, 3)
+    t = np.asarray(surface.triangles.detach().cpu(), dtype=np.int64).reshape(-1, 3)
+    uv = np.asarray(atlas.uv.detach().cpu(), dtype=np.float64).reshape(-1, 2)
+    if len(uv) != 3 * len(t):
+        raise ValueError("write_surface_obj: the atlas was built from another surface")
+    if gamma is None:
+        from .metrics import apply_gamma_curve as gamma
+    host = lambda x: np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32)
+    tex = {k: host(textures[k]).reshape(W, W, -1) for k in TEXTURE_KEYS}
+    maps = {"basecolor": host(gamma(textures["basecolor"])).reshape(W, W, 3), "roughness": tex["roughness"], "metallic": tex["metallic"],
+            "emission": tex["emission"], "normal": tex["normal"] * np.float32(0.5) + np.float32(0.5)}
+    files = [stem + ".obj", stem + ".mtl"]
+    lines = [f"mtllib {name}.mtl", "usemtl surface"]
+    lines += [f"v {x!r} {y!r} {z!r}" for x, y, z in v.tolist()]
+    lines += [f"vt {a!r} {1.0 - b!r}" for a, b in uv.tolist()]
+    lines += [f"f {a + 1}/{3 * f + 1} {b + 1}/{3 * f + 2} {c + 1}/{3 * f + 3}" for f, (a, b, c) in enumerate(t.tolist())]
+    with open(files[0], "w") as f:
+        f.write("\n".join(lines) + "\n")
+    keys = (("map_Kd", "basecolor"), ("map_Pr", "roughness"), ("map_Pm", "metallic"), ("map_Ke", "emission"), ("norm", "normal"))
+    with open(files[1], "w") as f:
+        f.write("newmtl surface\nKd 1 1 1\nKe 1 1 1\n" + "".join(f"{key} {name}_{k}.png\n" for key, k in keys))
+    for _, k in keys:
+        files.append(f"{stem}_{k}.png")
+        with open(files[-1], "wb") as f:
+            f.write(png_bytes(quantise8(maps[k])))
+    files.append(stem + "_emission.hdr")
+    with open(files[-1], "wb") as f:
+        f.write(hdr_bytes(tex["emission"]))
+    files.append(stem + "_emission.npy")
+    np.save(files[-1], tex["emission"])
+    return files
 
 
 VERTEX_PROPERTIES = ["x", "y", "z", "nx", "ny", "nz", "basecolor_r", "basecolor_g", "basecolor_b", "roughness", "metallic",
@@ -694,4 +922,5 @@ def write_surface_ply(path, surface: Surface, face_source: Optional[torch.Tensor
 
 __all__ = ["Surface", "SourceReport", "extract_surface", "emissive_sources", "simplify_surface", "write_surface_ply",
            "source_samples", "source_visibility", "SourceLights", "source_lights", "direct_light", "lit_view", "VERTEX_PROPERTIES",
-           "hemisphere_directions", "environment_light", "vertex_env_radiance"]
+           "hemisphere_directions", "environment_light", "vertex_env_radiance", "TEXTURE_KEYS", "bake_materials", "bake_irradiance",
+           "face_normals", "write_surface_obj", "png_bytes", "hdr_bytes", "quantise8"]

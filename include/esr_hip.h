@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 45
+#define ESR_ABI_VERSION 46
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -1899,6 +1899,89 @@ int esr_surface_env(const esr_bvh_node_t *nodes, int64_t n_faces, const double *
                     const float *p_normal, const int32_t *p_face, const float *p_base, const float *p_rough,
                     const float *p_metal, const float *p_wo, int32_t mode, double t_min, float *out, int32_t *n_open,
                     uint8_t *hit, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * W. Texture atlas of the surface (esr_nerf_amd/atlas.py: build, sample; sources.py: bake_materials, bake_irradiance,
+ *    lit_view(atlas=, textures=), write_surface_obj): every face gets a chart of its own in a square atlas, the texels know
+ *    their face, barycentrics and world point, and a texture is looked up bilinearly at a point of a face.  Nothing in the
+ *    reference corresponds to it.
+ * ------------------------------------------------------------------------- */
+
+#define ESR_ATLAS_MIN_SIZE     64     /* smallest and                                                                  */
+#define ESR_ATLAS_MAX_SIZE     8192   /* largest side W of the atlas, a power of two                                    */
+#define ESR_ATLAS_MAX_LEVELS   16     /* entries of a level table (the levels themselves are at most 13: 2^13 = 8192)   */
+#define ESR_ATLAS_MAX_CHANNELS 16     /* most channels of a texture (ESR_ECAP beyond it)                                */
+
+/*
+ * Layout (all integer).  W = size, g = gutter >= 1, lmin <= l <= lmax with 2^lmin >= 3 g + 2 and 2^lmax <= W.  A face of
+ * level l owns one half of a square cell of side s = 2^l texels.  With local texel indices (i, j), i along x, the texel
+ * centres at (i + 0.5, j + 0.5):
+ *   half 0 owns the texels with i + j <= s - 1, half 1 the rest;  leg(l) = s - (3 g + 1);
+ *   half 0's triangle is a = (g, g), b = (g + leg, g), c = (g, g + leg) in local texel units,
+ *   half 1's the point reflection p -> (s - p.x, s - p.y) of it.
+ * Footprint property: for every point p of a half's triangle the four texels (floor(p - 0.5) and + 1 per axis) of a bilinear
+ * lookup are owned by that half and lie inside the cell (tests/test_atlas_host.py enumerates it).
+ * A level table is int64 [ESR_ATLAS_MAX_LEVELS], indexed by the level itself.  From counts cnt_l:  n_l = ceil(cnt_l / 2) cells;
+ * the groups descend with the level: rank start S_l = sum_{l' > l} cnt_l', unit start U_l = sum_{l' > l} n_l' 4^(l' - lmin)
+ * in cells of side 2^lmin; the layout fits iff U_lmin + n_lmin <= (W / 2^lmin)^2.  The face at sorted rank k, S_l <= k < S_l +
+ * cnt_l, r = k - S_l, has cell r >> 1 and half r & 1; its unit u = U_l + (r >> 1) 4^(l - lmin); the cell's origin is
+ * (x0, y0) = 2^lmin (even bits of u, odd bits of u) (Z-order).
+ *
+ * Common to the entries: size, gutter, lmin, lmax as above (else ESR_EINVAL, as for a NULL or misaligned pointer -- f64 / i64:
+ * 8 bytes, the rest: 4 -- or a negative size); ESR_ECAP for n_faces or n_vertices >= 2^31.  A face with a vertex id outside
+ * [0, n_vertices) is read nowhere: level lmin, rot 0, its texels' point (and tex) NaN.  One launch on `stream` each; nothing
+ * waits on the host; no float atomics: the same input gives the same bytes.
+ *
+ * esr_atlas_levels.  vertices f64 [V,3], triangles i64 [F,3].  Per face with the corners a, b, c, in binary64, every written
+ * operation rounded once, no contraction:
+ *   e1 = b - a, e2 = c - a, n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), c2 = (n0 n0 + n1 n1) + n2 n2
+ *   level[f] = the smallest l in [lmin, lmax] with (double)(leg(l)^2) (double)(leg(l)^2) >= c2 rho4, or lmax if there is none;
+ *              lmin if c2 is not finite.  rho4 = (rho^2)^2 for a density of rho texels per world unit (finite, >= 0).
+ *   rot[f] in {0, 1, 2}: with d_k = ((ex ex + ey ey) + ez ez) of the edge opposite corner k (c - b, c - a, b - a), the smallest
+ *              k with the largest d_k (d1 > d0, then d2 > max; a NaN compares false).  The corners in the order rot, rot + 1,
+ *              rot + 2 (mod 3) are the triangle's a, b, c: the longest edge becomes the hypotenuse.
+ *   hist i64 [16] (device): zeroed here, then hist[l] = the faces of level l (LDS partial per block, one integer atomic per
+ *              level).  level, rot i32 [F].
+ *
+ * esr_atlas_charts.  order i64 [F]: the faces sorted by descending level, by face id within a level (a stable sort of
+ * lmax - level); counts i64 [16] [host]: hist read back.  ESR_EINVAL if the counts are negative, lie outside lmin .. lmax or do
+ * not sum to n_faces; ESR_ECAP if the layout does not fit; nothing is written in either case.  One lane per rank k, f = order[k]:
+ *   chart i32 [F,4]: chart[f] = (x0, y0, l | half << 8 | rot << 16, k)
+ *   uv f32 [F,3,2]: corner j of the face is corner q = (j - rot) mod 3 of a, b, c; uv[f,j] = ((x0, y0) + that corner) / W
+ *              (exact: W is a power of two), x first.
+ *
+ * esr_atlas_texels.  The same order, rot and counts (the same refusals).  One lane per texel, the texel (i, j) at index
+ * j W + i:  m = the Z-order code of (i >> lmin, j >> lmin); the group l with U_l <= m < U_l + n_l 4^(l - lmin); the cell
+ * (m - U_l) >> 2 (l - lmin); (i_loc, j_loc) = (i, j) mod s; half = i_loc + j_loc >= s; r = 2 cell + half;
+ *   face i32 [W,W] = order[S_l + r], or -1 where there is no group or r >= cnt_l (the missing half of an odd group).
+ *   With hx = 2 i_loc + 1 - 2 g, hy = 2 j_loc + 1 - 2 g in half 0 and hx = 2 (s - g) - (2 i_loc + 1), hy likewise, in half 1:
+ *   beta = (double)hx / (double)(2 leg), gamma = (double)hy / (double)(2 leg): not clamped, the gutter carries the affine
+ *   extension.  bary f32 [W,W,2] = (float)beta, (float)gamma: the weights of the rotated corners b and c.
+ *   flags u8 [W,W]: bit 0 = inside the triangle, hx >= 0 and hy >= 0 and hx + hy <= 2 leg (integers).
+ *   point f32 [W,W,3] = (float)((a + beta (b - a)) + gamma (c - a)) per component in binary64 with the rotated corners.
+ *   tex f32 [W,W,C] with attr f32 [V,C], 1 <= C = channels <= ESR_ATLAS_MAX_CHANNELS (both or neither; NULL, NULL, 0
+ *   without): in binary32, (wa x_a + bf x_b) + gf x_c with bf = (float)beta, gf = (float)gamma, wa = (1 - bf) - gf.
+ *   A texel without a face has face -1 and 0 everywhere else.
+ *
+ * esr_atlas_sample.  n queries: q_face i32 [n], q_bary f64 [n,2], the weights of the face's second and third corner as a ray
+ * cast returns them.  tex f32 [W,W,C], out f32 [n,C].  A face outside [0, n_faces) (-1: no hit) gives 0.  In binary64:
+ *   w0 = (1 - bu) - bv;  u = (w0 uv[f,0].x + bu uv[f,1].x) + bv uv[f,2].x, v likewise;  x = u W - 0.5, y = v W - 0.5
+ *   (not finite: 0);  i0 = floor(x), fx = (float)(x - floor(x)), likewise j0, fy;  the indices i0, i0 + 1, j0, j0 + 1
+ *   clamped to [0, W - 1];  in binary32, with t_ij = tex[j, i]:
+ *   out = (t00 (1 - fx) + t10 fx) (1 - fy) + (t01 (1 - fx) + t11 fx) fy.
+ * ESR_ECAP for n >= 2^31 or C > ESR_ATLAS_MAX_CHANNELS; n == 0 succeeds and touches no pointer.
+ */
+int esr_atlas_levels(const double *vertices, int64_t n_vertices, const int64_t *triangles, int64_t n_faces, int32_t size,
+                     int32_t gutter, int32_t lmin, int32_t lmax, double rho4, int32_t *level, int32_t *rot, int64_t *hist,
+                     void *stream);
+int esr_atlas_charts(int64_t n_faces, const int64_t *order, const int32_t *rot, const int64_t *counts, int32_t size,
+                     int32_t gutter, int32_t lmin, int32_t lmax, int32_t *chart, float *uv, void *stream);
+int esr_atlas_texels(const double *vertices, int64_t n_vertices, const int64_t *triangles, int64_t n_faces,
+                     const int64_t *order, const int32_t *rot, const int64_t *counts, int32_t size, int32_t gutter,
+                     int32_t lmin, int32_t lmax, const float *attr, int32_t channels, int32_t *face, float *bary, float *point,
+                     uint8_t *flags, float *tex, void *stream);
+int esr_atlas_sample(const float *uv, int64_t n_faces, int32_t size, const float *tex, int32_t channels, int64_t n,
+                     const int32_t *q_face, const double *q_bary, float *out, void *stream);
 
 #ifdef __cplusplus
 }
