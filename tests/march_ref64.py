@@ -1,6 +1,7 @@
 """Float64 restatement of the ray march (csrc/march.hip: march_kernel, all four (COARSE, GA) variants) and of the plan
-(plan_kernel, plan_totals_kernel), used only by tests/test_gpu_march_ref64.py and tests/test_march_ref64_autograd.py; never
-imported by the product path.
+(plan_kernel, plan_totals_kernel), used only by the tests: tests/march_check.py (the comparison of a backend with this
+restatement, run by tests/test_gpu_march_ref64.py on the kernels and by tests/test_march_ref64_host.py on the CPU),
+tests/march_emu.py, tests/test_march_ref64_host.py and tests/test_march_ref64_autograd.py; never imported by the product path.
 
 What the kernel computes before any sum is formed -- ray geometry, sample positions, continuous grid indices and the clamped
 "grad"-mode tap indices -- is replayed in binary32, op for op (feat_ref64's replays); trilinear values, the finite differences,
@@ -23,7 +24,27 @@ Backward values carry a magnitude M (the same computation on magnitudes: every d
 and gw T - back / (1 - alpha)) plus these E terms through first-order products; the kernel's 1 / (1 - alpha + 1e-10) with an
 alpha uncertain by E_alpha adds |back| * (1 / (1 - min(1, alpha + U E_alpha) + 1e-10) - 1 / (1 - alpha + 1e-10)) / U, taken
 over the whole interval rather than from the derivative, since alpha can round to exactly 1.0f.  A cell is then checked as
-|gpu - ref| <= K * U * absref (K: the test file's).
+|gpu - ref| <= K * U * absref + FLOOR with K = K_FAMILY[family] (below): per family of values the smallest power of two that
+is at least twice the larger of the worst ratios measured for the kernel on the MI355X and for the emulation on the CPU;
+none exceeds 4 (the E terms are bounds, so most measured ratios are far below 1).
+
+That the bound has teeth is shown without a GPU (tests/test_march_ref64_host.py): march_emu.Emu is a binary32 emulation of all
+four variants of COUNT (plain, cached), FILL (plain, from the cache) and BWD (plain, dsdf_rec with accumulate 0 / 1, from the
+cache), written from the kernel in its operation order; march_check.check_variant finds it inside every bound with every
+flipped decision in its band on the GPU test's scenes, and rejects each of the 29 mutants of march_emu.MUTANTS (neighbours
+across gaps and chunk seams, the 1e-5 guards, the float transmittance product, the early stop, the coarse second pass, the
+"grad" taps, view directions and channels, the reverse scan's seed, guard, relu' and stopped sample, dsdf_rec, the cached
+fill, the record slots and their order, overflow rays) in every family the table lists for it.  Two of the usual errors are not built,
+each with its proof of equivalence in march_emu.py (the clamp of alpha at 1, and a folded out-of-range corner on the SDF
+grid -- on the mask grid it is built); the `<=` stop is not built because no transmittance of a host scene reaches its value.
+
+Stated limit: relu' = [pc > nc] is not a forced decision.  `near / den` in the backward's magnitudes is a first-order term
+(it is multiplied by K U like the rest): it covers a backend whose pc - nc differs in VALUE, not one whose relu' differs.
+Where prv == nxt bit for bit (a ray's only survivor, equal neighbours, ic == 0) restatement and kernel both see pc == nc
+and agree on relu' = 0, and a backend with relu' = [pc >= nc] is rejected (mutant bwd_relu_ge, host scene `flat`).  Where
+prv != nxt but the binary32 sigmoids tie -- e.g. a locally constant non-zero SDF whose fetched values differ by an ulp, under
+the backward from the cache -- a correct binary32 backend takes relu' = 0 where float64 takes 1 and is rejected; the scenes
+of both test files hold no such sample with a gradient that shows: kernel and emulation pass on all of them.
 """
 from __future__ import annotations
 
@@ -42,6 +63,27 @@ U = 2.0 ** -24
 DEC_K = 16                       # decision bands: DEC_K * U * E around the threshold
 T_STOP = float(torch.tensor(1e-3, dtype=F32))   # the kernel compares a binary32 T with 1e-3f
 KEY = 1 << 20                    # key = ray * KEY + step
+
+
+# K per family of march_check._bound: the smallest power of two that is at least twice the larger of the two measured worst
+# ratios |got - ref| / (2^-24 absref) -- the kernel's on the MI355X over the three scenes of test_march_against_float64 and
+# every cap of test_march_lds_regimes_and_refusal, and the emulation's (march_emu.Emu) over the seven host scenes of
+# test_march_ref64_host.py.  Families that measure alike share a line (the line's worst sets its K).  absref's E terms are
+# first-order BOUNDS, so most measured ratios are well below 1 and so is K.
+#                                                                                    measured worst:   kernel    emulation
+_K_GROUPS = [
+    (1, ["fine count last", "fine_ga count last", "coarse count last", "coarse_ga count last"]),     # 0.325     0.365
+    (0.5, ["coarse count cumw", "coarse_ga count cumw"]),                                            # 0.101     0.178
+    (0.5, ["fine cache sdf", "fine fill sdf", "fine_ga fill sdf", "coarse fill sdf", "coarse_ga fill sdf"]),   # 0.246     0.212
+    (1, ["fine cache alpha", "fine fill w", "fine_ga fill w", "coarse fill w", "coarse_ga fill w"]),  # 0.486     0.486
+    (0.125, ["fine bwd", "coarse bwd"]),                                                             # 0.041     0.061
+    (0.0625, ["fine_ga bwd", "coarse_ga bwd", "coarse_ga bwd grad_gg"]),                             # 0.018     0.022
+    (0.25, ["fine bwd_rec"]),                                                                        # 0.058     0.070
+    (1, ["fine bwd_cached"]),                            # (T and alpha binary32 inputs here: absref has no E of them)  0.397     0.405
+    (2, ["fine bwd_rec dsdf_rec"]),                                                                  # 0.749     0.763
+    (4, ["fine bwd_cached dsdf_rec"]),                                                               # 1.406     1.406
+]
+K_FAMILY = {f: k for k, fs in _K_GROUPS for f in fs}
 
 
 @dataclass
@@ -64,21 +106,6 @@ class Scene:
     @property
     def cap(self):
         return (self.max_steps + 63) // 64 * 64
-
-    def struct(self):
-        from esr_nerf_amd import _lib
-        sc = _lib.EsrScene()
-        for i in range(3):
-            sc.xyz_min[i], sc.xyz_max[i] = float(self.lo[i]), float(self.hi[i])
-            sc.mask_min[i], sc.mask_max[i] = float(self.mlo[i]), float(self.mhi[i])
-        sc.gx, sc.gy, sc.gz = self.dims
-        sc.mx, sc.my, sc.mz = self.mdims
-        sc.near_, sc.stepdist, sc.voxel_size = self.near, self.stepdist, self.vox
-        sc.act_shift, sc.mask_thres, sc.fast_thres, sc.s_val = self.act_shift, self.mask_thres, self.fast_thres, self.s_val
-        sc.max_steps = self.max_steps
-        for i, v in enumerate((0.5, 1.0, 1.5, 2.0)):
-            sc.grad_feat[i] = v
-        return sc
 
 
 def f32(v):
