@@ -1,5 +1,6 @@
 """Float64 restatement of the fine feature kernels (csrc/feat.hip: feat_fwd_kernel and feat_bwd_kernel) and a mirror of the
-backward's window bookkeeping, used only by tests/test_gpu_feat_scatter.py; never imported by the product path.
+backward's window bookkeeping, used by tests/feat_check.py (the comparison), tests/feat_emu.py (the binary32 emulation) and
+their two tests; never imported by the product path.
 
 What the kernels compute in binary32 before any sum is formed -- the sample position (the sampler's replay), its continuous
 grid index, the clamped stencil tap coordinates -- is replayed here in binary32, op for op (torch's float32 ops round each
@@ -22,12 +23,75 @@ import torch
 F32, F64 = torch.float32, torch.float64
 XROWS, DXROWS = 104, 64
 ROW_SDF, ROW_FEAT, ROW_NRM = 6, 7, 31
+ROW_XYZ, ROW_SIN, ROW_COS, ROW_VD, ROW_VSIN, ROW_VCOS = 43, 46, 61, 76, 79, 82
+COLOR_ROW = (0, 88, 96)          # first row of the three 6-row colour groups
+ZERO_ROWS = (85, 86, 87, 94, 95, 102, 103)
+U = 2.0 ** -24
 WIN_CELLS = 2560                 # feat.hip: WIN_CELLS
 SDF_GID = 0                      # grid id of the SDF gradient; colour grids: colour_gid(src, on)
 
 
 def colour_gid(src: int, on: bool) -> int:
     return 1 + 2 * src + (0 if on else 1)
+
+
+# K per family of feat_check: |got - ref| <= K * 2^-24 * absref + FLOOR.  Twice the larger of the two measured worst ratios
+# (feat_bwd / feat_fwd kernels on the MI355X, tests/test_gpu_feat_scatter.py -s; the binary32 emulation feat_emu.py on the
+# host cases, tests/test_feat_ref64_host.py -s), rounded up to a power of two, never above the 8 that K_BWD = K_FWD = 8 were.
+# colour and stencil: twice the measured worst is above 8, so they keep the 8 they had, with a margin of 1.9 and 1.7 instead of 2.
+# Their rounding model allows more than was seen: an 8-corner fma chain has three weight differences and two products per
+# corner and up to 8 roundings of partial sums, each <= 1 unit of 2^-24 * absref; 4.15 and 4.68 of those 13 were reached, by the
+# kernel and by the emulation on the same samples.  pe: the kernel's sincosf reaches 2.008 (just over 1 ulp of the result;
+# the emulation's correctly rounded sin / cos: 1.0), which the rule turns into 8.
+K_FAMILY = {
+    # family            K      measured worst: kernel / emulation
+    "colour":           8,   # 4.150 / 4.150   rows 0-5, 88-93, 96-101
+    "stencil":          8,   # 4.677 / 4.677   rows 7-30
+    "normal":           4,   # 1.018 / 1.018   rows 31-42 (scale: first order through the quotient and F.normalize)
+    "gnorm":            8,   # 3.286 / 2.703
+    "pe":               8,   # 2.008 / 0.996   rows 46-75, scale |ref|
+    "view":             4,   # 1.473 / 0.987   rows 76-84 (the input rows exactly)
+    "sdf fit":          8,   # 3.122 / 2.836   cells reached only by terms of lanes whose window fits
+    "sdf global":       8,   # 2.947 / 3.097   cells reached by at least one global-atomic term
+    "sdf grad4":        8,   # 3.312 / 2.356   cells reached by a grad4 term
+    "colour grid":      8,   # 3.150 / 3.092
+}
+# exact families (no K): "sdf value", "unit", "zero rows", "padding", "x16", "dsdf_out", "untouched", "finite"
+EXACT_FAMILIES = ("sdf value", "unit", "zero rows", "padding", "x16", "dsdf_out", "untouched", "finite")
+
+
+def row_families():
+    """family of each of the 104 rows of the X tile"""
+    fam = [None] * XROWS
+    for r0 in COLOR_ROW:
+        fam[r0:r0 + 6] = ["colour"] * 6
+    fam[ROW_SDF] = "sdf value"
+    fam[ROW_FEAT:ROW_FEAT + 24] = ["stencil"] * 24
+    fam[ROW_NRM:ROW_NRM + 12] = ["normal"] * 12
+    fam[ROW_XYZ:ROW_XYZ + 3] = ["unit"] * 3
+    fam[ROW_SIN:ROW_SIN + 30] = ["pe"] * 30
+    fam[ROW_VD:ROW_VD + 9] = ["view"] * 9
+    for r in ZERO_ROWS:
+        fam[r] = "zero rows"
+    assert None not in fam
+    return fam
+
+
+def round_bf16(x64):
+    """float64 -> the nearest bfloat16 value (ties to even), as float64; one rounding (no detour through binary32)"""
+    m, e = torch.frexp(x64)
+    return torch.ldexp(torch.round(m * 256.0) / 256.0, e)
+
+
+X16_SLOT = [8 * ((s >> 1) & 3) + 2 * (s >> 3) + (s & 1) for s in range(32)]     # sample -> slot of the row-quad tile
+
+
+def x16_decode(q):
+    """esr_fine_feat_fwd_x16's tile [tiles, 26, 32 slots, 4 rows in quad] -> rows 0..95 [tiles, 96, 32 samples] and the two
+    alternate quads [tiles, 8, 32] (rows 88..93, 6, 7), as float64"""
+    tiles = q.shape[0]
+    q = q.double()[:, :, X16_SLOT, :]
+    return q[:, :24].permute(0, 1, 3, 2).reshape(tiles, 96, 32), q[:, 24:26].permute(0, 1, 3, 2).reshape(tiles, 8, 32)
 
 
 @dataclass
@@ -61,6 +125,12 @@ class Case:
     sdf: Optional[torch.Tensor] = None   # [X, Y, Z] float32
     color_on: Optional[torch.Tensor] = None   # group-0 colour grid [X, Y, Z, 6] on on-tiles / other tiles
     color_off: Optional[torch.Tensor] = None
+    color_on1: Optional[torch.Tensor] = None  # groups 1 and 2 (rows 88-93, 96-101): any of them absent
+    color_on2: Optional[torch.Tensor] = None
+    color_off1: Optional[torch.Tensor] = None
+    color_off2: Optional[torch.Tensor] = None
+    viewdirs: Optional[torch.Tensor] = None   # per ray [R, 3] (record mode; None: rays_d normalised)
+    pt_viewdirs: Optional[torch.Tensor] = None  # per point [n_pts, 3] (explicit points; None: zeros)
     srcs: List[Src] = field(default_factory=list)
     grad_sdf: bool = True
     dsdf_extra: Optional[torch.Tensor] = None  # [tiles*32]
@@ -71,6 +141,21 @@ class Case:
     @property
     def n_pts(self):
         return 0 if self.pts is None else self.pts.shape[0]
+
+    def colour_grids(self, on: bool):
+        return [self.color_on, self.color_on1, self.color_on2] if on else [self.color_off, self.color_off1, self.color_off2]
+
+    def view_inputs(self):
+        """the view direction per sample slot [tiles*32, 3] binary32 (padding lanes: 0)"""
+        n = self.tiles_all * 32
+        v = torch.zeros(n, 3, dtype=torch.float32)
+        if self.pts is not None:
+            if self.pt_viewdirs is not None:
+                v[:self.n_pts] = self.pt_viewdirs
+            return v
+        vd = self.viewdirs if self.viewdirs is not None else torch.nn.functional.normalize(self.rays_d, dim=-1)
+        r = self.rec_ray.long()
+        return torch.where((r >= 0)[:, None], vd[r.clamp_min(0)], v)
 
     def launch_range(self):
         """esr_fine_feat_bwd's [t_begin, t_end) (feat.hip, the host entry)."""
@@ -202,20 +287,33 @@ def fetch(grid64, dims, ix32, ch=1):
 
 # ---- forward ----------------------------------------------------------------------------------------------------------
 def forward_rows(case: Case, p, valid):
-    """Rows 0..42 of the X tile and gnorm per sample (valid samples only): float64 values and per-element error scales
-    (|x - ref| <= K 2^-24 scale is the check).  Normal rows: first-order propagation of the taps' scales through the
-    difference quotient and F.normalize (|d n| <= 2 |d g| / |g|)."""
+    """All 104 rows of the X tile and gnorm per sample (valid samples only): float64 values and per-element error scales
+    (|x - ref| <= K 2^-24 scale is the check; scale 0: the row is exact).  Normal rows: first-order propagation of the taps'
+    scales through the difference quotient and F.normalize (|d n| <= 2 |d g| / |g|).  `unit` is replayed in binary32
+    (__fdiv_rn(p - lo, hi - lo)); the sin / cos rows are float64 sin / cos of the binary32 argument unit * 2^i (an exact
+    product) with scale |ref|: sinf / cosf are within 2 ulp of the result (shade_ref64.py's model).  View rows: the input and its
+    float64 sin / cos.  Zero rows, the SDF value row and the view input rows are exact."""
     dims = case.dims
     ind = world_to_index(case, p[valid])
     M = ind.shape[0]
     t = torch.nonzero(valid)[:, 0] // 32
     on = t < case.tiles_on
-    val = torch.zeros(M, 43, dtype=F64)
-    scl = torch.zeros(M, 43, dtype=F64)
-    for grid, sel in ((case.color_on, on), (case.color_off, ~on)):
-        if grid is not None and bool(sel.any()):
-            v, a = fetch(grid.double().reshape(-1, 6), dims, ind[sel], ch=6)
-            val[sel, 0:6], scl[sel, 0:6] = v, a
+    val = torch.zeros(M, XROWS, dtype=F64)
+    scl = torch.zeros(M, XROWS, dtype=F64)
+    for is_on, sel in ((True, on), (False, ~on)):
+        for gi, grid in enumerate(case.colour_grids(is_on)):
+            if grid is not None and bool(sel.any()):
+                v, a = fetch(grid.double().reshape(-1, 6), dims, ind[sel], ch=6)
+                val[sel, COLOR_ROW[gi]:COLOR_ROW[gi] + 6], scl[sel, COLOR_ROW[gi]:COLOR_ROW[gi] + 6] = v, a
+    unit = _r(_r(p[valid].double() - case.lo.double()).double() / _r(case.hi.double() - case.lo.double()).double())
+    val[:, ROW_XYZ:ROW_XYZ + 3] = unit.double()
+    arg = unit.double()[:, :, None] * (2.0 ** torch.arange(5, dtype=F64))          # [M, 3, 5]: coordinate-major
+    assert torch.equal(arg, arg.float().double())
+    val[:, ROW_SIN:ROW_SIN + 15], val[:, ROW_COS:ROW_COS + 15] = torch.sin(arg).reshape(M, 15), torch.cos(arg).reshape(M, 15)
+    vd = case.view_inputs()[valid].double()
+    val[:, ROW_VD:ROW_VD + 3], val[:, ROW_VSIN:ROW_VSIN + 3], val[:, ROW_VCOS:ROW_VCOS + 3] = vd, torch.sin(vd), torch.cos(vd)
+    for r0, n in ((ROW_SIN, 15), (ROW_COS, 15), (ROW_VSIN, 3), (ROW_VCOS, 3)):
+        scl[:, r0:r0 + n] = val[:, r0:r0 + n].abs()
     sdfv = case.pt_sdf if case.pts is not None else case.rec_sdf
     sv = torch.zeros(case.tiles_all * 32, dtype=F32)
     sv[:sdfv.shape[0]] = sdfv
@@ -385,13 +483,14 @@ def _colour_terms(case: Case, ind, t, s, src: Src, absmode):
     return fl.reshape(M, 48), (w[:, :, None] * d6[:, None, :]).reshape(M, 48)
 
 
-def _accumulate(flat, val, aval, tile):
+def _accumulate(flat, val, aval, tile, lane, g4):
+    """terms -> cells; the raw terms keep their tile, sample slot (tile * 32 + lane) and whether they are grad4 terms"""
     keep = (flat >= 0) & (aval != 0)
-    flat, val, aval, tile = flat[keep], val[keep], aval[keep], tile[keep]
+    flat, val, aval, tile, lane, g4 = flat[keep], val[keep], aval[keep], tile[keep], lane[keep], g4[keep]
     u, inv = torch.unique(flat, return_inverse=True)
     v = torch.zeros(u.numel(), dtype=F64).index_add_(0, inv, val)
     a = torch.zeros(u.numel(), dtype=F64).index_add_(0, inv, aval)
-    return (u, v, a), (flat, val, aval, tile)
+    return (u, v, a), (flat, val, aval, tile, lane, g4)
 
 
 def scatter(case: Case, X, gnorm, p=None, valid=None, ind=None):
@@ -413,8 +512,10 @@ def scatter(case: Case, X, gnorm, p=None, valid=None, ind=None):
         gn = gnorm[t].gather(2, s[:, None, None].expand(-1, 4, 1))[..., 0]
         f, v = _sdf_terms(case, ind, t, s, nrow, gn, False)
         _, a = _sdf_terms(case, ind, t, s, nrow, gn, True)
+        is_g4 = (torch.arange(f.shape[1]) >= 72)[None].expand_as(f)          # 3 bars x 4 corners x 6 cells, then grad4's 8
         cells[SDF_GID], terms[SDF_GID] = _accumulate(f.reshape(-1), v.reshape(-1), a.reshape(-1),
-                                                     t[:, None].expand_as(f).reshape(-1))
+                                                     t[:, None].expand_as(f).reshape(-1),
+                                                     jj[:, None].expand_as(f).reshape(-1), is_g4.reshape(-1))
         if case.dsdf_out:
             dsdf = dsdf_rows32(case, t, s), jj
     for k, src in enumerate(case.srcs):
@@ -428,7 +529,9 @@ def scatter(case: Case, X, gnorm, p=None, valid=None, ind=None):
             _, a = _colour_terms(case, ind[m], t[m], s[m], src, True)
             gid = colour_gid(k, is_on)
             cells[gid], terms[gid] = _accumulate(f.reshape(-1), v.reshape(-1), a.reshape(-1),
-                                                 t[m][:, None].expand_as(f).reshape(-1))
+                                                 t[m][:, None].expand_as(f).reshape(-1),
+                                                 jj[m][:, None].expand_as(f).reshape(-1),
+                                                 torch.zeros_like(f, dtype=torch.bool).reshape(-1))
     return Scatter(cells, terms, dsdf)
 
 
@@ -467,12 +570,14 @@ def _windows(segs, dims, below, above, ch):
     return res, base
 
 
-CLASSES = ("fit", "cut8_fit", "cut8_global", "global", "mixed", "clip_lo", "clip_hi", "colour_only")
+CLASSES = ("fit", "cut8_fit", "cut8_global", "global", "mixed", "clip_lo", "clip_hi", "colour_only", "small_norm")
 
 
-def census(case: Case, p=None, valid=None):
-    """Per tile of the launch range: segments, probe total, cut8, window per segment and phase, and the path classes
-    (CLASSES) the tile takes.  Returns (per-tile list of dicts, {class: tile count})."""
+def census(case: Case, p=None, valid=None, gnorm=None):
+    """Per tile of the launch range: segments, probe total, cut8, window per segment and phase, the `has` flag per lane and
+    phase, and the path classes (CLASSES) the tile takes.  `small_norm`: a valid lane of the tile takes the |g| <= 1e-12
+    branch of the backward for some radius (needs `gnorm` [tiles, 4, 32], the forward's output; SDF launches only).
+    Returns (per-tile list of dicts, {class: tile count})."""
     if p is None:
         p, valid = positions(case)
     dims = case.dims
@@ -523,8 +628,13 @@ def census(case: Case, p=None, valid=None):
                 cls.add("clip_hi")
         if not case.grad_sdf:
             cls.add("colour_only")
+        elif gnorm is not None and bool((gnorm[t][:, torch.from_numpy(v)] <= 1e-12).any()):
+            cls.add("small_norm")
         for c in cls:
             counts[c] += 1
-        tiles.append(dict(tile=t, segs=[(a, b) for a, b, _, _ in segs], probe=total, cut8=cut8,
+        heads = [a for a, _, _, _ in segs]
+        seg_of = [max([n for n, a in enumerate(heads) if a <= s_], default=-1) if v[s_] else -1 for s_ in range(32)]
+        has = {k: [bool(v[s_]) and w[seg_of[s_]][0] for s_ in range(32)] for k, w in phases.items()}
+        tiles.append(dict(tile=t, segs=[(a, b) for a, b, _, _ in segs], probe=total, cut8=cut8, has=has,
                           windows={k: [f for f, _, _ in w] for k, w in phases.items()}, classes=sorted(cls)))
     return tiles, counts
