@@ -553,6 +553,118 @@ def vertex_env_radiance(surface: Surface, env, dirs=128, bvh=None) -> torch.Tens
                              a["metallic"].float().reshape(-1), n, dirs=dirs, bvh=bvh)
 
 
+MAX_PATHS = _lib.SURFACE_PATH_MAX_PATHS
+MAX_PATH_DEPTH = _lib.SURFACE_PATH_MAX_DEPTH
+PATH_CHUNK = 1 << 20                     # most points of one launch of path_light
+
+
+@torch.no_grad()
+def path_light(surface: Surface, report: SourceReport, points: torch.Tensor, normals: torch.Tensor, faces=None, basecolor=None,
+               roughness=None, metallic=None, wo=None, env=None, paths: int = 64, depth: int = 2, samples: int = 16, edits=None,
+               seed: int = 0, mode: int = 0, bvh=None, chunk: int = PATH_CHUNK, t_min: float = 1e-6, eps: float = 1e-6,
+               return_trace: bool = False, lights=None):
+    """Path-traced light at the surface points ``points`` [P, 3] with the unit shading normals ``normals`` [P, 3]
+    (``esr_surface_path``, section X of include/esr_hip.h): ``paths`` paths per point of up to ``depth`` segments.  Every
+    segment takes a uniform random direction in the hemisphere of its vertex's normal (the light-transport stage's
+    ``diffuse_scattering``; Philox4x32-10 keyed by ``seed``, the counter names point, path and segment) and weights the path by
+    the Disney reflection there; a segment that leaves the mesh collects the environment ``env`` (as ``environment_light`` takes
+    it; None: no environment) and ends the path; at every vertex a segment reaches, one random sample of every source of
+    ``report`` (``source_lights(surface, report, samples, edits)``, or ``lights`` where the caller holds them already) is gathered
+    with ``direct_light``'s term and shadow segment.
+
+    ``mode`` 0: the radiance reflected towards ``wo`` [P, 3] by ``basecolor`` [P, 3], ``roughness`` [P], ``metallic`` [P];
+    ``mode`` 1: the irradiance at the point (the first vertex weighs by cos 2 pi instead; no material, no ``wo``).
+    ``faces`` int32 [P]: the face each point lies on, which its first segment never hits (-1: none).  The vertices a path
+    reaches take the surface's per-vertex normal, basecolor, roughness and metallic, interpolated.
+
+    -> dict of float32 [P, 3] ``env_dir`` (the environment seen directly from the point), ``env_indir`` (the environment by way
+    of other surface points), ``src_indir`` (the sources by way of other surface points; their direct light is
+    ``direct_light``'s) and float32 [P] ``open``, the share of first segments that leave the mesh.  ``return_trace`` adds
+    ``trace`` int32 [P, paths, depth] (the face each segment hit, -1 where it left the mesh, -2 where it was not cast) and
+    ``end`` uint8 [P, paths] (0 the depth is used up, 1 left the mesh, 2 reached a back face).
+
+    Points beyond ``chunk`` go in several launches that give the bytes of one.  Limits: the sources are point samples with
+    ``direct_light``'s near-field clamp, no sampling inside faces, a fixed depth without Russian roulette and without
+    importance sampling of the BRDF.  The same input gives the same bytes on every call; nothing is read back."""
+    import ctypes
+    from . import raycast
+    what = "path_light"
+    v = surface.vertices
+    dev = v.device
+    for name, x, lo, hi in (("paths", paths, 1, MAX_PATHS), ("depth", depth, 1, MAX_PATH_DEPTH), ("mode", mode, 0, 1)):
+        if isinstance(x, bool) or not isinstance(x, int) or not lo <= x <= hi:
+            raise ValueError(f"{what}: {name} is an integer in {lo} .. {hi}, got {x!r}")
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"{what}: seed is an integer in 0 .. 2^64 - 1, got {seed!r}")
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+        raise ValueError(f"{what}: chunk is a positive count of points, got {chunk!r}")
+    samples = int(samples)
+    if samples < 1 or samples > MAX_LIGHT_SLOTS:
+        raise ValueError(f"{what}: 1 .. {MAX_LIGHT_SLOTS} samples per source, got {samples}")
+    if not float(t_min) >= 0.0:
+        raise ValueError(f"{what}: t_min is not negative, got {t_min}")
+    if not 0.0 <= float(eps) < 0.5:
+        raise ValueError(f"{what}: eps is in [0, 0.5), got {eps}")
+    sg = [None, None, None] if env is None else _env_parameters(what, env, dev)
+    if not isinstance(points, torch.Tensor) or points.dim() != 2:
+        raise ValueError(f"{what}: points must be a float [P, 3] tensor on the surface's device")
+    P = int(points.shape[0])
+    _light_input(what, "points", points, (P, 3), dev)
+    _light_input(what, "normals", normals, (P, 3), dev)
+    if P >= 2 ** 31:
+        raise ValueError(f"{what}: {P} points exceed the kernel's 31-bit count")
+    if faces is not None:
+        _light_input(what, "faces", faces, (P,), dev, dtypes=(torch.int32,))
+    mat = [None] * 4
+    if mode == 0:
+        if basecolor is None or roughness is None or metallic is None or wo is None:
+            raise ValueError(f"{what}: mode 0 needs basecolor, roughness, metallic and wo")
+        mat = [_light_input(what, name, x, shape, dev).float().contiguous()
+               for name, x, shape in (("basecolor", basecolor, (P, 3)), ("roughness", roughness, (P,)), ("metallic", metallic, (P,)),
+                                      ("wo", wo, (P, 3)))]
+    V = int(v.shape[0])
+    attrs = []
+    for key, width in (("normal", 3), ("basecolor", 3), ("roughness", 1), ("metallic", 1)):
+        x = surface.attrs.get(key)
+        if not isinstance(x, torch.Tensor) or x.device != dev or x.numel() != V * width:
+            raise ValueError(f"{what}: the surface carries no per-vertex {key}")
+        attrs.append(x.float().reshape(V, width).contiguous())
+    if bvh is None:
+        bvh = raycast.build(v, surface.triangles)
+    elif not isinstance(bvh, raycast.Bvh) or bvh.vertices.device != dev:
+        raise ValueError(f"{what}: bvh is the raycast.Bvh of the surface")
+    if lights is None:
+        lights = source_lights(surface, report, samples, edits)
+    elif not isinstance(lights, SourceLights) or lights.point.device != dev:
+        raise ValueError(f"{what}: lights is the SourceLights of source_lights on the surface's device")
+    S, kp = len(lights), lights.slots
+    out = torch.zeros(P, 3, 3, dtype=torch.float32, device=dev)
+    n_open = torch.zeros(P, dtype=torch.int32, device=dev)
+    trace = torch.zeros(P, paths, depth, dtype=torch.int32, device=dev) if return_trace else None
+    end = torch.zeros(P, paths, dtype=torch.uint8, device=dev) if return_trace else None
+    if P:
+        pts, nrm = points.double().contiguous(), normals.float().contiguous()
+        fc = None if faces is None else faces.contiguous()
+        arrays = [x.contiguous() for x in (lights.point, lights.normal, lights.weight, lights.radiance, lights.face)]
+        signed = seed - 2 ** 64 if seed >= 2 ** 63 else seed               # (the 64 bits, as the int64 the entry takes)
+        cut = lambda x, a, b: None if x is None else _lib.ptr(x[a:b])
+        with torch.cuda.device(dev):
+            for p0 in range(0, P, chunk):
+                p1 = min(P, p0 + chunk)
+                _lib.check(_lib.lib().esr_surface_path(
+                    _lib.ptr(bvh.nodes), bvh.n_faces, _lib.ptr(bvh.vertices), int(bvh.vertices.shape[0]), _lib.ptr(bvh.triangles),
+                    _lib.ptr(attrs[0]), _lib.ptr(attrs[1]), _lib.ptr(attrs[2]), _lib.ptr(attrs[3]), S, kp, _lib.ptr(arrays[0]),
+                    _lib.ptr(arrays[1]), _lib.ptr(arrays[2]), _lib.ptr(arrays[3]), _lib.ptr(arrays[4]), float(eps), _lib.ptr(sg[0]),
+                    _lib.ptr(sg[1]), _lib.ptr(sg[2]), 0 if env is None else int(sg[0].shape[0]), p1 - p0, cut(pts, p0, p1),
+                    cut(nrm, p0, p1), cut(fc, p0, p1), cut(mat[0], p0, p1), cut(mat[1], p0, p1), cut(mat[2], p0, p1),
+                    cut(mat[3], p0, p1), mode, paths, depth, float(t_min), signed, p0, cut(out, p0, p1), cut(n_open, p0, p1),
+                    cut(trace, p0, p1), cut(end, p0, p1), _lib.stream_ptr(dev)), "esr_surface_path")
+    res = {"env_dir": out[:, 0], "env_indir": out[:, 1], "src_indir": out[:, 2], "open": n_open.float() / float(paths)}
+    if return_trace:
+        res["trace"], res["end"] = trace, end
+    return res
+
+
 def _hit_points(surface: Surface, hit, d):
     """What ``lit_view`` knows at the nearest hits ``hit`` (``raycast.Hits``) of the rays with the directions ``d``: the point
     (float64, NaN where the ray misses: such a point is lit by nothing), the unit shading normal, the interpolated
@@ -577,7 +689,7 @@ def _hit_points(surface: Surface, hit, d):
 
 @torch.no_grad()
 def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: int = 16, edits=None, bvh=None, env=None,
-             env_dirs=128, bounces: int = 0, atlas=None, textures=None):
+             env_dirs=128, bounces: int = 0, atlas=None, textures=None, paths=None, depth: int = 2, seed: int = 0):
     """View ``view`` of ``cams`` lit by the (edited) sources, without an optimiser step: the nearest face of every pixel
     (the rays and the walk of ``raycast.cast_cameras``), the vertex attributes interpolated with the hit's barycentrics in
     torch (the normal normalised again), ``wo`` = minus the unit pixel ray, and ``direct_light`` with ``source_lights(surface,
@@ -607,7 +719,17 @@ def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: i
     With ``atlas`` and ``textures`` (``atlas.build`` of this surface and the dict of ``bake_materials``; both or neither) the
     basecolor, roughness, metallic, emission and the shading normal of every pixel are looked up in the textures
     (``atlas.sample`` at the hit's face and barycentrics; the normal normalised again) instead of interpolated from the
-    vertices; ``face`` and ``depth`` are unchanged.  With None the keys and bytes are those of the vertex path."""
+    vertices; ``face`` and ``depth`` are unchanged.  With None the keys and bytes are those of the vertex path.
+
+    With ``paths`` (a count; ``depth`` segments, ``seed``) the light beyond the first reflection is path-traced
+    (``path_light`` with the pixel's point as the first vertex): ``lin/env_dir``, ``lin/env_indir`` and ``etc/open`` come from
+    the paths (``env`` may be None: they are 0 then), ``env_dirs`` is unused, ``bounces`` must be left at 0, and
+
+    ``lin/src_indir`` float32 [H, W, 3]  the sources' light that reaches the pixel's point by way of other surface points
+
+    is added; the linear image is ``lin/emit + lin/reflect + lin/src_indir + lin/env_dir + lin/env_indir``.  ``atlas`` and
+    ``textures`` affect the first vertex only: the vertices a path reaches take the per-vertex attributes.  With
+    ``paths=None`` the keys and bytes are exactly those described above."""
     from . import raycast
     from .relight import edit_emission
     what = "lit_view"
@@ -625,7 +747,17 @@ def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: i
     if cams.device != dev:
         raise ValueError(f"{what}: the surface and the cameras are on one device")
     tables = _edit_tables(what, S, edits, dev) if edits else None
-    if env is not None:
+    if paths is not None:
+        if isinstance(bounces, bool) or bounces != 0:
+            raise ValueError(f"{what}: with paths the bounces are the paths': bounces stays 0, got {bounces!r}")
+        for name, x, lo, hi in (("paths", paths, 1, MAX_PATHS), ("depth", depth, 1, MAX_PATH_DEPTH)):
+            if isinstance(x, bool) or not isinstance(x, int) or not lo <= x <= hi:
+                raise ValueError(f"{what}: {name} is an integer in {lo} .. {hi}, got {x!r}")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+            raise ValueError(f"{what}: seed is an integer in 0 .. 2^64 - 1, got {seed!r}")
+        if env is not None:
+            env = _env_parameters(what, env, dev)
+    elif env is not None:
         if isinstance(bounces, bool) or bounces not in (0, 1):
             raise ValueError(f"{what}: bounces is 0 or 1, got {bounces!r}")
         env = _env_parameters(what, env, dev)
@@ -639,7 +771,10 @@ def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: i
     if not t.shape[0]:                                                     # (no face: every ray misses)
         black = torch.zeros(H, W, 3, dtype=torch.float32, device=dev)
         res = {"lin/reflect": black, "lin/emit": black.clone(), "face": hit.face.reshape(H, W), "depth": hit.t.reshape(H, W)}
-        if env is not None:
+        if paths is not None:
+            res["lin/env_dir"], res["lin/env_indir"], res["lin/src_indir"] = black.clone(), black.clone(), black.clone()
+            res["etc/open"] = torch.zeros(H, W, dtype=torch.float32, device=dev)
+        elif env is not None:
             res["lin/env_dir"], res["etc/open"] = black.clone(), torch.zeros(H, W, dtype=torch.float32, device=dev)
             if bounces:
                 res["lin/env_indir"] = black.clone()
@@ -659,7 +794,13 @@ def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: i
     res = {"lin/reflect": torch.where(got[:, None], reflect, zero).reshape(H, W, 3),
            "lin/emit": torch.where(lit[:, None], emit, zero).reshape(H, W, 3),
            "face": hit.face.reshape(H, W), "depth": hit.t.reshape(H, W)}
-    if env is not None:
+    if paths is not None:
+        lit_by = path_light(surface, report, x, normal, hit.face, a["basecolor"], a["roughness"][:, 0], a["metallic"][:, 0], wo, env=env,
+                            paths=paths, depth=depth, samples=samples, edits=edits, seed=seed, bvh=bvh, lights=lights)
+        for k in ("env_dir", "env_indir", "src_indir"):
+            res["lin/" + k] = torch.where(got[:, None], lit_by[k], zero).reshape(H, W, 3)
+        res["etc/open"] = torch.where(got, lit_by["open"], zero[0, 0]).reshape(H, W)
+    elif env is not None:
         at = (x, normal, a["basecolor"], a["roughness"][:, 0], a["metallic"][:, 0], wo)
         direct, share = environment_light(surface, env, *at, dirs=env_dirs, faces=hit.face, bvh=bvh, return_open=True)
         res["lin/env_dir"] = torch.where(got[:, None], direct, zero).reshape(H, W, 3)

@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 46
+#define ESR_ABI_VERSION 47
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -1982,6 +1982,86 @@ int esr_atlas_texels(const double *vertices, int64_t n_vertices, const int64_t *
                      uint8_t *flags, float *tex, void *stream);
 int esr_atlas_sample(const float *uv, int64_t n_faces, int32_t size, const float *tex, int32_t channels, int64_t n,
                      const int32_t *q_face, const double *q_bary, float *out, void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * X. Path-traced light on the surface (esr_nerf_amd/sources.py: path_light, lit_view(paths=)): the light of the environment
+ *    and of the emissive sources that reaches a surface point over up to `depth` segments, every vertex of a path reflecting
+ *    by the Disney BRDF -- the light-transport stage's one-sample estimator (app/utils/pbr/functions.py:10-18,
+ *    diffuse_scattering: a uniform random unit vector flipped into the normal's hemisphere, weighted by the reflection with
+ *    its (n . wi) 2 pi), chained on the mesh.  A path lives in registers: nothing of size P N reaches memory but the optional
+ *    `trace` and `end`.
+ * ------------------------------------------------------------------------- */
+
+#define ESR_SURFACE_PATH_MAX_PATHS 4096   /* most paths of a point (ESR_ECAP beyond it) */
+#define ESR_SURFACE_PATH_MAX_DEPTH 8      /* most segments of a path (ESR_ECAP beyond it) */
+
+/*
+ * Scene.  nodes / n_faces / vertices / n_vertices / triangles exactly as esr_bvh_cast takes them.  Per-vertex attributes, f32:
+ * v_normal [V,3], v_base [V,3], v_rough [V], v_metal [V] (read only at the vertices of a face that a segment hits).
+ * Lights.  n_sources (S), slots (Kp), l_point, l_normal, l_weight, l_radiance, l_face, eps: the arrays of section U, with its
+ * rules.  n_sources == 0: no sources, none of them is read.
+ * Environment.  mus, lambdas, lobes, n_sg (J) as in section V.  n_sg == 0: no environment, none of them is read, nothing is
+ * added to the two environment components (they are exactly +0).
+ * Points.  The arrays of section V: p_point f64 [P,3], p_normal f32 [P,3], p_face i32 [P] or NULL, and in mode 0 p_base, p_rough,
+ * p_metal, p_wo: the first vertex of every path of the point.
+ * Controls.  mode 0 reflected radiance, 1 irradiance at the point; n_paths (N) in 1 .. ESR_SURFACE_PATH_MAX_PATHS; depth (D) in
+ * 1 .. ESR_SURFACE_PATH_MAX_DEPTH; t_min >= 0; seed: the 64 bits of the seed; point_base >= 0: the index of point 0 in the whole
+ * call a chunk belongs to (a chunked call gives the bytes of the whole call).
+ *
+ * Random numbers.  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85), key = (low,
+ * high word of seed), counter = ((uint32)(point_base + p), path s, 2 b + purpose, block) for segment b.  point_base + P <= 2^32.
+ * Direction (purpose 0), binary64, every operation rounded on its own: a word x gives a = 2 (x 2^-32) - 1; block k gives the
+ * candidate pairs (w0, w1) and (w2, w3); the first pair over the blocks 0 .. 7 with s = a1 a1 + a2 a2 < 1 is taken;
+ * q = sqrt(1 - s), w = (2 a1 q, 2 a2 q, 1 - 2 s) (Marsaglia's uniform point on the sphere); if none of the 16 passes, w =
+ * (0, 0, 1).  wi = (float)w.  Flip as in section V step 1 on wi and the vertex's normal n: s = (wi0 n0 + wi1 n1) + wi2 n2 in
+ * binary32, and s < 0 negates w and wi.
+ *
+ * Per path, the throughput T (binary64, per channel) starts at 1; per segment b = 0 .. D - 1 from the vertex (x, n, material,
+ * wo, face):
+ *   1. weight.  T_c = T_c Wt_c, Wt = (double)R of the binary32 Disney reflection for base, rough, metal, n, wi, wo (it carries
+ *      (n . wi) 2 pi); for b == 0 in mode 1 instead Wt = cos_x (2 pi), cos_x = (n0 wi0 + n1 wi1) + n2 wi2 in binary64 on the
+ *      widened values, the same for the three channels.
+ *   2. cast.  esr_bvh_cast's nearest-hit walk, o = x, d = w, t_min < t <= +inf, skip_face = face.
+ *   3. miss.  With n_sg > 0: L = the environment of section V step 3 along wi, binary32 in its order; T_c (double)L_c is added
+ *      to the component env_dir if b == 0, else to env_indir.  The path ends (code 1).
+ *   4. hit on face f with the barycentrics u, v:  wa = (1 - u) - v;  x' = (wa A + u B) + v C per coordinate in binary64;  the
+ *      attributes in binary32 with the three weights rounded once, (wa a_A + u a_B) + v a_C, no contraction;  n' = the normal
+ *      divided by its binary32 length sqrt((n0 n0 + n1 n1) + n2 n2): a length that is 0 or not finite ends the path (code 2);
+ *      wo' = -wi;  unless (n'0 wo'0 + n'1 wo'1) + n'2 wo'2 > 0 in binary32 the path ends (code 2: a back face).
+ *   5. next-event estimation, with n_sources > 0.  For every source s one slot k = word >> (32 - log2 Kp) (0 for Kp == 1) of
+ *      purpose 1, block s >> 2, word s & 3.  Its term is section U's per-slot term in mode 0 at (x', n', the interpolated
+ *      material, wo'): the same silence rules, the same G, the same shadow segment (skip_face = l_face), term_c.  T_c
+ *      ((double)Kp term_c) is added to the component src_indir.  A segment that hits a source's face adds no emission: the
+ *      lights account for it.
+ *   6. advance: (x', n', the interpolated material, wo', f) is the vertex of segment b + 1.  After segment D - 1 the path ends
+ *      (code 0).
+ * No Russian roulette; a lane walks at most N D (1 + S) rays.
+ *
+ * Sum, as section V step 5: Kd = min(64, the next power of two >= N) adjacent lanes per point; lane k adds its paths k, k + Kd,
+ * ... ascending into nine binary64 sums (component, channel; from +0.0), combined by the balanced pairwise sum over the lanes.
+ *   out f32 [P,3,3]: out[p, component, channel] = (float)(S / (double)N); components 0 env_dir, 1 env_indir, 2 src_indir.
+ * No atomics: the same input gives the same bytes on every call and under every chunking through point_base.
+ * Optional: n_open i32 [P], the paths whose segment 0 misses; trace i32 [P,N,D], the face hit by each segment, -1 where it left
+ * the mesh, -2 where it was not cast; end u8 [P,N], the code above.
+ *
+ * n_points == 0 (with every other argument valid) succeeds and touches no pointer.  ESR_EINVAL: a negative size, a mode other
+ * than 0 and 1, slots < 1 or not a power of two, eps not in [0, 0.5), n_paths < 1, depth < 1, t_min negative or NaN, point_base
+ * < 0, a NULL or misaligned required pointer (f64 / i64: 8 bytes, nodes: 16, the rest: 4; an optional pointer that is given is
+ * held to the same alignment; the attributes are required with n_faces > 0, the lights with n_sources > 0, the environment
+ * with n_sg > 0, the material of the points in mode 0).  ESR_ECAP: a size >= 2^31, slots > ESR_SURFACE_LIGHT_MAX_SLOTS, n_sg >
+ * ESR_SURFACE_ENV_MAX_SG, n_paths > ESR_SURFACE_PATH_MAX_PATHS, depth > ESR_SURFACE_PATH_MAX_DEPTH, point_base + n_points >
+ * 2^32.  Nothing is launched in either case.  One launch on `stream`; nothing waits on the host.
+ * Layout: a wave holds 64 / Kd points; the path's vertex and throughput stay in registers; the lobe table sits in LDS.
+ */
+int esr_surface_path(const esr_bvh_node_t *nodes, int64_t n_faces, const double *vertices, int64_t n_vertices,
+                     const int64_t *triangles, const float *v_normal, const float *v_base, const float *v_rough,
+                     const float *v_metal, int64_t n_sources, int32_t slots, const double *l_point, const double *l_normal,
+                     const double *l_weight, const float *l_radiance, const int32_t *l_face, double eps, const float *mus,
+                     const float *lambdas, const float *lobes, int32_t n_sg, int64_t n_points, const double *p_point,
+                     const float *p_normal, const int32_t *p_face, const float *p_base, const float *p_rough,
+                     const float *p_metal, const float *p_wo, int32_t mode, int32_t n_paths, int32_t depth, double t_min,
+                     int64_t seed, int64_t point_base, float *out, int32_t *n_open, int32_t *trace, uint8_t *end,
+                     void *stream);
 
 #ifdef __cplusplus
 }
