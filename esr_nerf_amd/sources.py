@@ -562,7 +562,7 @@ PATH_CHUNK = 1 << 20                     # most points of one launch of path_lig
 def path_light(surface: Surface, report: SourceReport, points: torch.Tensor, normals: torch.Tensor, faces=None, basecolor=None,
                roughness=None, metallic=None, wo=None, env=None, paths: int = 64, depth: int = 2, samples: int = 16, edits=None,
                seed: int = 0, mode: int = 0, bvh=None, chunk: int = PATH_CHUNK, t_min: float = 1e-6, eps: float = 1e-6,
-               return_trace: bool = False, lights=None):
+               return_trace: bool = False, lights=None, sampling: str = "uniform", roulette=None):
     """Path-traced light at the surface points ``points`` [P, 3] with the unit shading normals ``normals`` [P, 3]
     (``esr_surface_path``, section X of include/esr_hip.h): ``paths`` paths per point of up to ``depth`` segments.  Every
     segment takes a uniform random direction in the hemisphere of its vertex's normal (the light-transport stage's
@@ -583,9 +583,18 @@ def path_light(surface: Surface, report: SourceReport, points: torch.Tensor, nor
     ``trace`` int32 [P, paths, depth] (the face each segment hit, -1 where it left the mesh, -2 where it was not cast) and
     ``end`` uint8 [P, paths] (0 the depth is used up, 1 left the mesh, 2 reached a back face).
 
+    ``sampling`` "brdf" (``esr_surface_path_is``, section Y) draws every segment's direction from the vertex's BRDF instead: a
+    cosine-distributed direction or the specular lobe's half vector, chosen by the material and weighted by one-sample multiple
+    importance sampling -- the same expectation at far less noise, with other random numbers and so other bytes than
+    "uniform".  There ``roulette=k`` (an integer >= 1) starts Russian roulette at segment ``k``: a path goes on with the
+    probability max(throughput) clamped to [1/16, 1] and is weighted by its inverse; None: no roulette.  ``end`` then also holds
+    3 (ended by the roulette) and 4 (the draw left the hemisphere: no light comes from there).  ``roulette`` with "uniform" is
+    refused.
+
     Points beyond ``chunk`` go in several launches that give the bytes of one.  Limits: the sources are point samples with
-    ``direct_light``'s near-field clamp, no sampling inside faces, a fixed depth without Russian roulette and without
-    importance sampling of the BRDF.  The same input gives the same bytes on every call; nothing is read back."""
+    ``direct_light``'s near-field clamp, no sampling inside faces; with the default ``sampling`` a fixed depth without Russian
+    roulette and without importance sampling of the BRDF.  The same input gives the same bytes on every call; nothing is read
+    back."""
     import ctypes
     from . import raycast
     what = "path_light"
@@ -598,6 +607,7 @@ def path_light(surface: Surface, report: SourceReport, points: torch.Tensor, nor
         raise ValueError(f"{what}: seed is an integer in 0 .. 2^64 - 1, got {seed!r}")
     if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
         raise ValueError(f"{what}: chunk is a positive count of points, got {chunk!r}")
+    rr_start = _path_sampling(what, sampling, roulette, depth)
     samples = int(samples)
     if samples < 1 or samples > MAX_LIGHT_SLOTS:
         raise ValueError(f"{what}: 1 .. {MAX_LIGHT_SLOTS} samples per source, got {samples}")
@@ -648,21 +658,35 @@ def path_light(surface: Surface, report: SourceReport, points: torch.Tensor, nor
         arrays = [x.contiguous() for x in (lights.point, lights.normal, lights.weight, lights.radiance, lights.face)]
         signed = seed - 2 ** 64 if seed >= 2 ** 63 else seed               # (the 64 bits, as the int64 the entry takes)
         cut = lambda x, a, b: None if x is None else _lib.ptr(x[a:b])
+        entry = "esr_surface_path" if rr_start is None else "esr_surface_path_is"
+        controls = (mode, paths, depth) if rr_start is None else (mode, paths, depth, rr_start)
         with torch.cuda.device(dev):
             for p0 in range(0, P, chunk):
                 p1 = min(P, p0 + chunk)
-                _lib.check(_lib.lib().esr_surface_path(
+                _lib.check(getattr(_lib.lib(), entry)(
                     _lib.ptr(bvh.nodes), bvh.n_faces, _lib.ptr(bvh.vertices), int(bvh.vertices.shape[0]), _lib.ptr(bvh.triangles),
                     _lib.ptr(attrs[0]), _lib.ptr(attrs[1]), _lib.ptr(attrs[2]), _lib.ptr(attrs[3]), S, kp, _lib.ptr(arrays[0]),
                     _lib.ptr(arrays[1]), _lib.ptr(arrays[2]), _lib.ptr(arrays[3]), _lib.ptr(arrays[4]), float(eps), _lib.ptr(sg[0]),
                     _lib.ptr(sg[1]), _lib.ptr(sg[2]), 0 if env is None else int(sg[0].shape[0]), p1 - p0, cut(pts, p0, p1),
                     cut(nrm, p0, p1), cut(fc, p0, p1), cut(mat[0], p0, p1), cut(mat[1], p0, p1), cut(mat[2], p0, p1),
-                    cut(mat[3], p0, p1), mode, paths, depth, float(t_min), signed, p0, cut(out, p0, p1), cut(n_open, p0, p1),
-                    cut(trace, p0, p1), cut(end, p0, p1), _lib.stream_ptr(dev)), "esr_surface_path")
+                    cut(mat[3], p0, p1), *controls, float(t_min), signed, p0, cut(out, p0, p1), cut(n_open, p0, p1),
+                    cut(trace, p0, p1), cut(end, p0, p1), _lib.stream_ptr(dev)), entry)
     res = {"env_dir": out[:, 0], "env_indir": out[:, 1], "src_indir": out[:, 2], "open": n_open.float() / float(paths)}
     if return_trace:
         res["trace"], res["end"] = trace, end
     return res
+
+
+def _path_sampling(what, sampling, roulette, depth):
+    """-> None for "uniform" (section X), else section Y's ``rr_start``: ``roulette``, or ``depth`` (no roulette) for None"""
+    if sampling not in ("uniform", "brdf"):
+        raise ValueError(f'{what}: sampling is "uniform" or "brdf", got {sampling!r}')
+    if roulette is not None:
+        if sampling == "uniform":
+            raise ValueError(f'{what}: roulette comes with sampling="brdf"')
+        if isinstance(roulette, bool) or not isinstance(roulette, int) or not 1 <= roulette < 2 ** 31:
+            raise ValueError(f"{what}: roulette is the first segment it runs at, an integer >= 1, or None; got {roulette!r}")
+    return None if sampling == "uniform" else (depth if roulette is None else roulette)
 
 
 def _hit_points(surface: Surface, hit, d):
@@ -689,7 +713,8 @@ def _hit_points(surface: Surface, hit, d):
 
 @torch.no_grad()
 def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: int = 16, edits=None, bvh=None, env=None,
-             env_dirs=128, bounces: int = 0, atlas=None, textures=None, paths=None, depth: int = 2, seed: int = 0):
+             env_dirs=128, bounces: int = 0, atlas=None, textures=None, paths=None, depth: int = 2, seed: int = 0,
+             sampling: str = "uniform", roulette=None):
     """View ``view`` of ``cams`` lit by the (edited) sources, without an optimiser step: the nearest face of every pixel
     (the rays and the walk of ``raycast.cast_cameras``), the vertex attributes interpolated with the hit's barycentrics in
     torch (the normal normalised again), ``wo`` = minus the unit pixel ray, and ``direct_light`` with ``source_lights(surface,
@@ -728,8 +753,9 @@ def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: i
     ``lin/src_indir`` float32 [H, W, 3]  the sources' light that reaches the pixel's point by way of other surface points
 
     is added; the linear image is ``lin/emit + lin/reflect + lin/src_indir + lin/env_dir + lin/env_indir``.  ``atlas`` and
-    ``textures`` affect the first vertex only: the vertices a path reaches take the per-vertex attributes.  With
-    ``paths=None`` the keys and bytes are exactly those described above."""
+    ``textures`` affect the first vertex only: the vertices a path reaches take the per-vertex attributes.  ``sampling`` and
+    ``roulette`` are ``path_light``'s ("brdf": directions drawn from the BRDF, the same keys at far less noise; they need
+    ``paths``).  With ``paths=None`` the keys and bytes are exactly those described above."""
     from . import raycast
     from .relight import edit_emission
     what = "lit_view"
@@ -755,8 +781,11 @@ def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: i
                 raise ValueError(f"{what}: {name} is an integer in {lo} .. {hi}, got {x!r}")
         if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
             raise ValueError(f"{what}: seed is an integer in 0 .. 2^64 - 1, got {seed!r}")
+        _path_sampling(what, sampling, roulette, depth)
         if env is not None:
             env = _env_parameters(what, env, dev)
+    elif sampling != "uniform" or roulette is not None:
+        raise ValueError(f"{what}: sampling and roulette are the paths': they need paths")
     elif env is not None:
         if isinstance(bounces, bool) or bounces not in (0, 1):
             raise ValueError(f"{what}: bounces is 0 or 1, got {bounces!r}")
@@ -796,7 +825,8 @@ def lit_view(surface: Surface, report: SourceReport, cams, view: int, samples: i
            "face": hit.face.reshape(H, W), "depth": hit.t.reshape(H, W)}
     if paths is not None:
         lit_by = path_light(surface, report, x, normal, hit.face, a["basecolor"], a["roughness"][:, 0], a["metallic"][:, 0], wo, env=env,
-                            paths=paths, depth=depth, samples=samples, edits=edits, seed=seed, bvh=bvh, lights=lights)
+                            paths=paths, depth=depth, samples=samples, edits=edits, seed=seed, bvh=bvh, lights=lights, sampling=sampling,
+                            roulette=roulette)
         for k in ("env_dir", "env_indir", "src_indir"):
             res["lin/" + k] = torch.where(got[:, None], lit_by[k], zero).reshape(H, W, 3)
         res["etc/open"] = torch.where(got, lit_by["open"], zero[0, 0]).reshape(H, W)
@@ -880,7 +910,7 @@ def bake_materials(surface: Surface, atlas, model=None, chunk: int = 1 << 18) ->
 
 @torch.no_grad()
 def bake_irradiance(surface: Surface, atlas, report: SourceReport, samples: int = 16, edits=None, env=None, env_dirs=128, bvh=None,
-                    chunk: int = 1 << 18) -> Dict[str, torch.Tensor]:
+                    chunk: int = 1 << 18, paths=None, depth: int = 2, seed: int = 0, roulette=None) -> Dict[str, torch.Tensor]:
     """The irradiance at the texels of ``atlas`` whose centre lies inside their face, with the face's geometric unit normal:
 
     ``light/sources`` float32 [W, W, S, 3]  ``direct_light(per_source=True)`` without ``wo``: per source, so that an intensity
@@ -888,10 +918,24 @@ def bake_irradiance(surface: Surface, atlas, report: SourceReport, samples: int 
     ``light/env``     float32 [W, W, 3]     only with ``env``: ``environment_light`` without ``wo`` over ``env_dirs``, the
                                             texel's own face skipped as ``lit_view`` skips the hit face
 
-    0 at every other texel.  ``chunk`` texels per launch."""
+    ``light/paths``   float32 [W, W, 3, 3]  only with ``paths`` (a count; ``depth`` segments, ``seed``, ``roulette``): the
+                                            path-traced irradiance, ``path_light(mode=1, sampling="brdf")`` -- its components
+                                            env_dir, env_indir, src_indir in this order, the texel's own face skipped by the
+                                            first segment; ``env`` may be None (the two environment components are 0 then)
+
+    0 at every other texel.  ``chunk`` texels per launch (the paths' bytes do not depend on it)."""
     from . import raycast
     what = "bake_irradiance"
     _check_atlas(what, surface, atlas)
+    if paths is not None:
+        for name, x, lo, hi in (("paths", paths, 1, MAX_PATHS), ("depth", depth, 1, MAX_PATH_DEPTH)):
+            if isinstance(x, bool) or not isinstance(x, int) or not lo <= x <= hi:
+                raise ValueError(f"{what}: {name} is an integer in {lo} .. {hi}, got {x!r}")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+            raise ValueError(f"{what}: seed is an integer in 0 .. 2^64 - 1, got {seed!r}")
+        _path_sampling(what, "brdf", roulette, depth)
+    elif roulette is not None:
+        raise ValueError(f"{what}: roulette is the paths': it needs paths")
     v, t = surface.vertices, surface.triangles
     W, dev, S = atlas.size, v.device, len(report)
     if bvh is None:
@@ -918,6 +962,12 @@ def bake_irradiance(surface: Surface, atlas, report: SourceReport, samples: int 
     out["light/sources"] = src.reshape(W, W, S, 3)
     if env is not None:
         out["light/env"] = out["light/env"].reshape(W, W, 3)
+    if paths is not None:
+        lit = path_light(surface, report, pts, nrm, face.contiguous(), env=env, paths=paths, depth=depth, samples=samples, edits=edits,
+                         seed=seed, mode=1, bvh=bvh, chunk=step, lights=lights, sampling="brdf", roulette=roulette)
+        traced = torch.zeros(W * W, 3, 3, dtype=torch.float32, device=dev)
+        traced[idx] = torch.stack([lit["env_dir"], lit["env_indir"], lit["src_indir"]], 1)
+        out["light/paths"] = traced.reshape(W, W, 3, 3)
     return out
 
 

@@ -37,7 +37,7 @@ extern "C" {
 
 #define ESR_TILE 32       /* samples per tile of the tile-major activation layout  */
 
-#define ESR_ABI_VERSION 47
+#define ESR_ABI_VERSION 48
 int esr_abi_version(void);          /* ESR_ABI_VERSION: bumps whenever a signature below changes */
 const char *esr_build_info(void);   /* "gfx950 <date>"                         */
 
@@ -2062,6 +2062,90 @@ int esr_surface_path(const esr_bvh_node_t *nodes, int64_t n_faces, const double 
                      const float *p_metal, const float *p_wo, int32_t mode, int32_t n_paths, int32_t depth, double t_min,
                      int64_t seed, int64_t point_base, float *out, int32_t *n_open, int32_t *trace, uint8_t *end,
                      void *stream);
+
+/* ------------------------------------------------------------------------- *
+ * Y. Importance-sampled path-traced light on the surface (esr_nerf_amd/sources.py: path_light(sampling="brdf"),
+ *    lit_view(paths=, sampling="brdf"), bake_irradiance(paths=)): section X's quantity -- the same integrand, the same
+ *    components, the same next-event estimation -- with every segment's direction drawn from the vertex's BRDF instead of
+ *    uniformly: a cosine-distributed direction or a half vector from the specular lobe D = exp(kappa (n.h - 1)) / (pi r^2),
+ *    kappa = 2 / r^2 (a von Mises-Fisher lobe, whose CDF in n.h inverts in closed form), combined by one-sample multiple
+ *    importance sampling with the balance heuristic, and Russian roulette from segment rr_start on.  The reference has no such
+ *    sampler: like sections U, W and X's chaining this is an addition to its interfaces.  It estimates what section X
+ *    estimates: p > 0 wherever the integrand is not 0, but for the lobe draws with oh' <= 0 that the density step below drops
+ *    (a loss of the order 1e-7 of a reflection, and only under a wo below the horizon).
+ * ------------------------------------------------------------------------- */
+
+/*
+ * Arguments: those of esr_surface_path with their rules, and rr_start (after depth): the first segment at which the roulette
+ * runs, >= 1; a value >= depth means no roulette.
+ *
+ * Random numbers.  Philox4x32-10 with section X's key; counter = ((uint32)(point_base + p), path s, 4 b + purpose, block) for
+ * segment b.  Purpose 0: the disc pair, blocks 0 .. 7.  Purpose 1: the next-event slots, block s >> 2, word s & 3, exactly as X.
+ * Purpose 2, block 0: word 0 is the technique's, word 1 the roulette's; a word x gives u = ((double)x + 0.5) 2^-32 (exact; never
+ * 0, never 1): u_t, u_r.  Purpose 3 is not used.
+ *
+ * Everything below is binary64 on the widened binary32 values (n, wo, base, rough, metal of the vertex), every operation
+ * rounded on its own, no contraction, sums of three terms as (a + b) + c; exp and log are the device library's binary64
+ * functions (under an ulp, not correctly rounded).  Per path the throughput T starts at 1; per segment b = 0 .. D - 1 from the
+ * vertex (x, n, material, wo, face), in this order:
+ *
+ *   Disc pair.  X's candidates: a = 2 (x 2^-32) - 1, block k gives the pairs (w0, w1) and (w2, w3); the first pair over the
+ *      blocks 0 .. 7 with s = a1 a1 + a2 a2, 0 < s < 1, is taken: (a1, a2, s).  If none of the 16 passes the local direction
+ *      below is (0, 0, 1) in either technique (a1 = a2 = 0, s = 0 for the cosine, s = 1 for the lobe).
+ *   Roulette, for b >= rr_start.  m = maxNum(maxNum(T0, T1), T2) (a NaN channel is passed over); q = m clamped to [1/16, 1],
+ *      q = 1 if m is NaN.  u_r >= q ends the path (code 3: segment b is not cast).  Otherwise T_c = T_c / q.
+ *   Frame (Duff et al.).  sg = copysign(1, nz), a = -1 / (sg + nz), b = (nx ny) a,
+ *      t1 = (1 + ((sg nx) nx) a, sg b, -(sg nx)), t2 = (b, sg + (ny ny) a, -ny).  A local (lx, ly, lz) is the world vector
+ *      (lx t1_i + ly t2_i) + lz n_i per coordinate.
+ *   Technique.  abar = ((base0 + base1) + base2) / 3, Fbar = 0.04 (1 - m) + abar m, dbar = (1 - m) abar, sum = Fbar + dbar;
+ *      q_s = Fbar / sum clamped to [1/8, 7/8] if sum > 0, else (and for a NaN) 1/8.  In mode 1 at b == 0, q_s = 0.
+ *      kappa = 2 / max(rough rough, 1e-7), e = 1 / exp(kappa) (0 where exp(kappa) is +inf).  The lobe is taken iff u_t < q_s.
+ *   Cosine technique.  w = the world vector of (a1, a2, sqrt(1 - s)) (Malley; not normalised again).
+ *   Lobe technique.  c = 1 + log(s + (1 - s) e) / kappa clamped to [0, 1]; sin = sqrt((1 - c)(1 + c)); the local half vector
+ *      h = ((a1 sin) / sqrt(s), (a2 sin) / sqrt(s), c), taken to the world; oh = (wo0 h0 + wo1 h1) + wo2 h2; unless oh > 0 the
+ *      path ends (code 4); w = (2 oh) h_i - wo_i, divided by its length sqrt((w0 w0 + w1 w1) + w2 w2).
+ *   Density, one code path for both techniques, at the w taken.  cos = (n0 w0 + n1 w1) + n2 w2; unless cos > 0 the path ends
+ *      (code 4: the integrand is 0 there, nothing is lost; a NaN ends it too).  wi = (float)w.
+ *      hv = w + wo, h' = hv / sqrt((hv0 hv0 + hv1 hv1) + hv2 hv2), nh = max(n . h', 0), oh' = wo . h';
+ *      A direction of the lobe technique with oh' <= 0 ends the path as well (code 4).  For unit vectors oh' = oh; but n and wo
+ *      are unit only to binary32 (|wo| = 1 + d, |d| up to about 1e-7) while w is normalised in binary64, so hv = w + wo carries
+ *      a term of the size d along wo and oh' = (oh + d / 2) / |h'| to first order: where w + wo cancels (oh -> 0, w -> -wo, which
+ *      only a wo under the horizon of n lets pass the test on cos) oh' is negative for a positive oh up to about 3e-4.  There the
+ *      density would not see the lobe that drew w, and the weight would be that of the cosine technique alone, thousands of
+ *      times too large.  Dropping these draws loses integrand that is not 0, so the estimate is low by their share: the
+ *      weight of such a draw is proportional to oh, the lobe's mass with oh < 3e-4 times that weight is of the order 1e-7 of a
+ *      reflection -- under the binary32 rounding of the reflection itself.  This step is not in the technique's definition
+ *      above; it is what makes "one code path for the density" safe.
+ *      With p_s = kappa / (2 pi (1 - e)) exp(kappa (nh - 1)) / (4 oh') the lobe technique's density of w (0 unless oh' > 0)
+ *      and p_c = cos / pi the cosine technique's, p = q_s p_s + (1 - q_s) p_c is the density of the direction taken (one-sample
+ *      MIS, balance heuristic; p >= p_c / 8 > 0).  Computed is 2 pi p, which needs no constant:
+ *      P_s = ((kappa / (1 - e)) exp(kappa (nh - 1))) / (4 oh') if oh' > 0, else 0;  P = q_s P_s + (1 - q_s) (2 cos).
+ *   1. weight.  T_c = T_c ((double)R_c / P) with R the binary32 Disney reflection of section X for wi (it carries
+ *      (n . wi) 2 pi).  In mode 1 at b == 0 instead T_c = T_c pi (the binary64 pi), the exact constant: the cosine technique's
+ *      density is the integrand's.
+ *   2. - 6.  Exactly section X's: cast (o = x, d = w), miss (code 1), hit and the next vertex (code 2), next-event estimation
+ *      with the point-light term (its purpose word is 4 b + 1), advance; after segment D - 1 the path ends (code 0).
+ * A lane walks at most N D (1 + S) rays.
+ *
+ * Sum and outputs: section X's -- Kd lanes per point, lane-strided binary64 sums from +0.0, the balanced pairwise sum over the
+ * lanes, out f32 [P,3,3] = (float)(S / (double)N); n_open i32 [P]; trace i32 [P,N,D] (-2 for a segment that was not cast, the
+ * one at which code 3 or 4 ended the path included); end u8 [P,N] with X's codes and 3 (the roulette), 4 (no direction in the
+ * hemisphere).  No atomics: the same input gives the same bytes on every call and under every chunking through point_base.
+ *
+ * n_points == 0 (with every other argument valid) succeeds and touches no pointer.  ESR_EINVAL: rr_start < 1, and every case
+ * of section X.  ESR_ECAP: as section X.  Nothing is launched in either case.  One launch on `stream`; nothing waits on the
+ * host.  Layout as section X: the vertex and the throughput stay in registers, the lobe table sits in LDS; the frame, the
+ * uniforms and the binary64 exp / log live only until the cast.
+ */
+int esr_surface_path_is(const esr_bvh_node_t *nodes, int64_t n_faces, const double *vertices, int64_t n_vertices,
+                        const int64_t *triangles, const float *v_normal, const float *v_base, const float *v_rough,
+                        const float *v_metal, int64_t n_sources, int32_t slots, const double *l_point, const double *l_normal,
+                        const double *l_weight, const float *l_radiance, const int32_t *l_face, double eps, const float *mus,
+                        const float *lambdas, const float *lobes, int32_t n_sg, int64_t n_points, const double *p_point,
+                        const float *p_normal, const int32_t *p_face, const float *p_base, const float *p_rough,
+                        const float *p_metal, const float *p_wo, int32_t mode, int32_t n_paths, int32_t depth, int32_t rr_start,
+                        double t_min, int64_t seed, int64_t point_base, float *out, int32_t *n_open, int32_t *trace, uint8_t *end,
+                        void *stream);
 
 #ifdef __cplusplus
 }
